@@ -9,6 +9,14 @@ R50-I3D-NL + LFB-NL on synthetic 32 x 224^2 clips (BASELINE.json `metric`), one 
 Rank 0 prints ONE JSON line.  `value` is the whole-job clips/s with the inputs already resident in
 HBM (weak scaling: 8 clips per GPU, i.e. global batch 64 at 8 GPUs as the north star asks).
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `config`):
+nothing else.  Everything described below that is measured or checked beside the timed steps (`roofline*`,
+`host_enqueue_*`, `allreduce`, `parity`, the `*_path` sub-records, `cpu_baseline`, `--detail`) needs `--full`.
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files, before any of that
+runs: `loss`, `prob`, and `params_sample` / `grads_sample` -- the updated trainable parameters and their
+gradients in the reference layout, concatenated in name order, at a fixed seeded sample of positions
+(DUMP_SAMPLE) -- so that two builds fed the same arguments can be compared output for output.
+
 The default dtype is `mix` (split-bf16 forward on fp32 storage + fp16 backward): the
 fastest path whose outputs AND parameter gradients are inside the north star's 1e-3 at the benchmarked
 size (`parity`, quoted from the committed full-size comparison while the kernel sources are the ones it
@@ -51,6 +59,7 @@ FAMILY_KERNELS = collections.OrderedDict([
     ("tn_f32", "gemm_tn_kernel<float> (exact-fp32 MFMA conv WGRAD)"),
 ])
 HBM_PEAK_GBPS = 8000.0                           # HBM3E spec peak (same guide; ~6.3 TB/s measured copy)
+DUMP_SAMPLE, DUMP_SEED, DUMP_MAX_BYTES = 4 << 20, 0, 64 << 20   # --dump-outputs: positions drawn per sampled array, their seed, cap
 
 
 def parse():
@@ -101,7 +110,15 @@ def parse():
     ap.add_argument("--no-fp16-line", action="store_true", help="skip the extra fp16 path measurement")
     ap.add_argument("--bf16-steps", type=int, default=20, help="timed steps of the extra bf16 throughput-path measurement (BASELINE.json configs[1])")
     ap.add_argument("--no-bf16-line", action="store_true", help="skip the extra bf16 path measurement")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / check what lies beside the timed steps: rooflines, host enqueue time, the data-parallel "
+                         "report, parity quote, the other dtypes' sub-records and the CPU baseline (a plain run only times)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB)")
+    args = ap.parse_args()
+    if args.detail and not args.full:
+        ap.error("--detail needs --full (the per-launch table comes from the profiled step)")
+    return args
 
 
 def self_launch(args):
@@ -384,6 +401,29 @@ def traffic_record(args, clips):
             "read side x2 per MI355X_MICROARCH.md; not measured in this run)")
 
 
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the last train_step handed its caller, as float32 .npy files (module docstring)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = collections.OrderedDict()
+    for name in ("loss", "prob"):
+        if name in eng.env:
+            arrays[name] = eng.fetch(name)
+    names = sorted(eng.train_layout)
+    if names:
+        params = np.concatenate([eng.fetch_param(n).ravel() for n in names])
+        grads = np.concatenate([eng.fetch_grad(n).ravel() for n in names])
+        pick = np.unique(np.random.default_rng(DUMP_SEED).integers(0, params.size, DUMP_SAMPLE)) \
+            if params.size > DUMP_SAMPLE else slice(None)
+        arrays["params_sample"], arrays["grads_sample"] = params[pick], grads[pick]
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, "--dump-outputs: more than %d bytes" % DUMP_MAX_BYTES
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if "RANK" not in os.environ and not os.environ.get("VLFB_BENCH_CHILD") and (args.gpus > 1 or args.launch):
@@ -450,31 +490,9 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         elapsed = float(t.item())
-    # host-side cost of enqueuing one step (untimed extra step): if this approaches ms_per_step the
-    # loop is launch-bound and wants HIP-graph capture
-    th0 = time.perf_counter()
-    eng.train_step(lr)
-    host_ms = (time.perf_counter() - th0) * 1e3
-    torch.cuda.synchronize()
-    loss = float(eng.fetch("loss").reshape(-1)[0])
-    host_path = "recorded call list (Engine.STEP_TRACE)" if eng._trace is not None else "step objects"
-    # ---- live roofline of the GEMM kernel families (this rank): ONE more step, behind the timed region, with HIP-event
-    # brackets around every GEMM launch on the stream it goes to, in the normal two-stream schedule (events cannot sit
-    # inside a recorded / replayed step, so this step is enqueued launch by launch)
-    fam, rows = profile_step(eng, lr, hip, torch)
-    traffic, traffic_source = traffic_record(args, clips)
-    if args.detail and rank == 0:
-        with open(args.detail, "w") as fh:
-            agg = collections.OrderedDict()
-            for sec, flops, tag in rows:
-                a = agg.setdefault(tag, [0.0, 0.0, 0])
-                a[0] += sec; a[1] += flops; a[2] += 1
-            fh.write("%10s %8s %6s %9s  %s\n" % ("total_us", "TFLOP/s", "calls", "GFLOP", "launch"))
-            for tag, (sec, flops, n) in sorted(agg.items(), key=lambda kv: -kv[1][0]):
-                fh.write("%10.1f %8.1f %6d %9.2f  %s\n" % (sec * 1e6, flops / sec / 1e12, n, flops / 1e9, tag))
-    step_flops = sum(f["flops"] for f in fam.values())
-    step_mfma_flops = sum(f["mfma_flops"] for f in fam.values())
-    nt_key, tn_key = dominant(fam, "nt"), dominant(fam, "tn")
+    loss = float(eng.fetch("loss").reshape(-1)[0])      # (the last timed step's)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
     clips_total = clips * world * args.steps
     value = clips_total / elapsed
@@ -493,76 +511,103 @@ def main():
                                 + ((" [" + " ".join(args.set) + "]") if args.set else ""),
                     "parallelism": "dp%d" % world, "final_loss": loss,
                     "arithmetic": DTYPE_NOTES[args.dtype]}),
-        ("roofline", roof_record(nt_key, fam, traffic, traffic_source)),
-        ("roofline_wgrad", roof_record(tn_key, fam, traffic, traffic_source)),
-        ("roofline_families", collections.OrderedDict((k, roof_record(k, fam, traffic, traffic_source, brief=True))
-                                                      for k in FAMILY_KERNELS if k in fam)),
-        # algorithmic FLOP of every contraction the step launched (this rank's plan: convs, attention products, head) per
-        # wall second against the 16-bit MFMA peak of all GPUs; and the same with every product counted as the MFMA
-        # instructions it is executed with (3 per split-bf16 product, 2 per two-term DGRAD product)
-        ("model_flops_utilisation", round(step_flops * args.steps / elapsed / 1e12 / MFMA16_PEAK, 4)),
-        ("mfma_flops_utilisation", round(step_mfma_flops * args.steps / elapsed / 1e12 / MFMA16_PEAK, 4)),
-        ("gflop_per_step_per_gpu", round(step_flops / 1e9, 1)),
-        ("host_enqueue_ms_per_step", round(host_ms, 2)),
-        ("host_enqueue_path", host_path),
     ])
-    if eng.comm is not None:       # the gradient exchange of this job (None on a one-process run without a process group)
-        out["allreduce"] = data_parallel_report(eng, args, lr, elapsed / args.steps, device)
-    out["parity"] = parity_record(args.workload, args.dtype)
-
-    # The other paths on the same workload, so that every number quoted next to a parity claim exists in THIS line:
-    #   mix_path   (when --dtype is not mix): the default path, see the module docstring
-    #   fp16_path:  16-bit storage and MFMA operands end to end -- the throughput path; gradients 15x outside the gate
-    #   split_path: fp32 storage, every contraction as split-bf16 products (three MFMAs per product) -- 25x inside it
-    #   fp32_path:  the same with the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32, 1/16 of the 16-bit matrix rate)
-    def extra_path(dtype, steps):
-        eng2 = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED)
-        eng2.plan(collections.OrderedDict((k, v.shape) for k, v in batch.items() if k in model.input_blob_names))
-        eng2.feed_params(synth.params(model, seed=cfg.RNG_SEED))
-        for k, v in batch.items():
-            if k in model.input_blob_names:
-                eng2.feed(k, v)
-        eng2.train_step(lr)
-        eng2.train_step(lr)
+    if args.full:
+        # ---- everything beside the timed steps.  Host-side cost of enqueuing one step (untimed extra step): if this
+        # approaches ms_per_step the loop is launch-bound and wants HIP-graph capture
+        th0 = time.perf_counter()
+        eng.train_step(lr)
+        host_ms = (time.perf_counter() - th0) * 1e3
         torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        for _ in range(steps):
+        host_path = "recorded call list (Engine.STEP_TRACE)" if eng._trace is not None else "step objects"
+        # ---- live roofline of the GEMM kernel families (this rank): ONE more step, behind the timed region, with HIP-event
+        # brackets around every GEMM launch on the stream it goes to, in the normal two-stream schedule (events cannot sit
+        # inside a recorded / replayed step, so this step is enqueued launch by launch)
+        fam, rows = profile_step(eng, lr, hip, torch)
+        traffic, traffic_source = traffic_record(args, clips)
+        if args.detail and rank == 0:
+            with open(args.detail, "w") as fh:
+                agg = collections.OrderedDict()
+                for sec, flops, tag in rows:
+                    a = agg.setdefault(tag, [0.0, 0.0, 0])
+                    a[0] += sec; a[1] += flops; a[2] += 1
+                fh.write("%10s %8s %6s %9s  %s\n" % ("total_us", "TFLOP/s", "calls", "GFLOP", "launch"))
+                for tag, (sec, flops, n) in sorted(agg.items(), key=lambda kv: -kv[1][0]):
+                    fh.write("%10.1f %8.1f %6d %9.2f  %s\n" % (sec * 1e6, flops / sec / 1e12, n, flops / 1e9, tag))
+        step_flops = sum(f["flops"] for f in fam.values())
+        step_mfma_flops = sum(f["mfma_flops"] for f in fam.values())
+        nt_key, tn_key = dominant(fam, "nt"), dominant(fam, "tn")
+        out.update([
+            ("roofline", roof_record(nt_key, fam, traffic, traffic_source)),
+            ("roofline_wgrad", roof_record(tn_key, fam, traffic, traffic_source)),
+            ("roofline_families", collections.OrderedDict((k, roof_record(k, fam, traffic, traffic_source, brief=True))
+                                                          for k in FAMILY_KERNELS if k in fam)),
+            # algorithmic FLOP of every contraction the step launched (this rank's plan: convs, attention products, head) per
+            # wall second against the 16-bit MFMA peak of all GPUs; and the same with every product counted as the MFMA
+            # instructions it is executed with (3 per split-bf16 product, 2 per two-term DGRAD product)
+            ("model_flops_utilisation", round(step_flops * args.steps / elapsed / 1e12 / MFMA16_PEAK, 4)),
+            ("mfma_flops_utilisation", round(step_mfma_flops * args.steps / elapsed / 1e12 / MFMA16_PEAK, 4)),
+            ("gflop_per_step_per_gpu", round(step_flops / 1e9, 1)),
+            ("host_enqueue_ms_per_step", round(host_ms, 2)),
+            ("host_enqueue_path", host_path),
+        ])
+        if eng.comm is not None:       # the gradient exchange of this job (None on a one-process run without a process group)
+            out["allreduce"] = data_parallel_report(eng, args, lr, elapsed / args.steps, device)
+        out["parity"] = parity_record(args.workload, args.dtype)
+
+        # The other paths on the same workload, so that every number quoted next to a parity claim exists in THIS line:
+        #   mix_path   (when --dtype is not mix): the default path, see the module docstring
+        #   fp16_path:  16-bit storage and MFMA operands end to end -- the throughput path; gradients 15x outside the gate
+        #   split_path: fp32 storage, every contraction as split-bf16 products (three MFMAs per product) -- 25x inside it
+        #   fp32_path:  the same with the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32, 1/16 of the 16-bit matrix rate)
+        def extra_path(dtype, steps):
+            eng2 = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED)
+            eng2.plan(collections.OrderedDict((k, v.shape) for k, v in batch.items() if k in model.input_blob_names))
+            eng2.feed_params(synth.params(model, seed=cfg.RNG_SEED))
+            for k, v in batch.items():
+                if k in model.input_blob_names:
+                    eng2.feed(k, v)
             eng2.train_step(lr)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t2) / max(steps, 1)
-        fam2, _ = profile_step(eng2, lr, hip, torch)
-        fl2 = sum(f["flops"] for f in fam2.values())
-        rec = {"value": round(clips / dt, 3), "unit": "clips/s", "ms_per_step": round(dt * 1e3, 3), "steps": steps,
-               "dtype": dtype, "arithmetic": DTYPE_NOTES[dtype],
-               "model_flops_utilisation": round(fl2 / dt / 1e12 / MFMA16_PEAK, 4),
-               "roofline": roof_record(dominant(fam2, "nt"), fam2, {}, "none: PMC passes are made for the default dtype", brief=True),
-               "roofline_wgrad": roof_record(dominant(fam2, "tn"), fam2, {}, "none: PMC passes are made for the default dtype", brief=True),
-               "parity": parity_record(args.workload, dtype)}
-        del eng2
-        return rec
+            eng2.train_step(lr)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            for _ in range(steps):
+                eng2.train_step(lr)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t2) / max(steps, 1)
+            fam2, _ = profile_step(eng2, lr, hip, torch)
+            fl2 = sum(f["flops"] for f in fam2.values())
+            rec = {"value": round(clips / dt, 3), "unit": "clips/s", "ms_per_step": round(dt * 1e3, 3), "steps": steps,
+                   "dtype": dtype, "arithmetic": DTYPE_NOTES[dtype],
+                   "model_flops_utilisation": round(fl2 / dt / 1e12 / MFMA16_PEAK, 4),
+                   "roofline": roof_record(dominant(fam2, "nt"), fam2, {}, "none: PMC passes are made for the default dtype", brief=True),
+                   "roofline_wgrad": roof_record(dominant(fam2, "tn"), fam2, {}, "none: PMC passes are made for the default dtype", brief=True),
+                   "parity": parity_record(args.workload, dtype)}
+            del eng2
+            return rec
 
-    if world == 1:
-        del eng
-        torch.cuda.empty_cache()
-        for key, dtype, steps, skip in (("mix_path", "mix", args.mix_steps, args.no_mix_line),
-                                        ("fp16_path", "fp16", args.fp16_steps, args.no_fp16_line),
-                                        ("bf16_path", "bf16", args.bf16_steps, args.no_bf16_line),
-                                        ("split_path", "split", args.split_steps, args.no_split_line),
-                                        ("fp32_path", "fp32", args.fp32_steps, args.no_fp32_line)):
-            if skip or dtype == args.dtype:
-                continue
-            try:
-                out[key] = extra_path(dtype, steps)
-                torch.cuda.empty_cache()
-            except Exception as e:   # a report, never a gate
-                out[key] = {"value": None, "error": repr(e)}
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1:
+            del eng
+            torch.cuda.empty_cache()
+            for key, dtype, steps, skip in (("mix_path", "mix", args.mix_steps, args.no_mix_line),
+                                            ("fp16_path", "fp16", args.fp16_steps, args.no_fp16_line),
+                                            ("bf16_path", "bf16", args.bf16_steps, args.no_bf16_line),
+                                            ("split_path", "split", args.split_steps, args.no_split_line),
+                                            ("fp32_path", "fp32", args.fp32_steps, args.no_fp32_line)):
+                if skip or dtype == args.dtype:
+                    continue
+                try:
+                    out[key] = extra_path(dtype, steps)
+                    torch.cuda.empty_cache()
+                except Exception as e:   # a report, never a gate
+                    out[key] = {"value": None, "error": repr(e)}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.workload, args.frames, args.crop, max(args.rois_per_clip, 3), args.dtype, device)
             except Exception as e:  # the baseline is a report, never a gate
                 out["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": os.cpu_count(), "kind": "port",
                                        "sample": "failed: %r" % (e,)}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     dist.barrier()
     if dist.initialized():

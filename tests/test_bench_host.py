@@ -55,6 +55,14 @@ def test_roofline_record_prices_a_family_against_the_mfma_peak_per_product():
     assert "source" not in r and bench.roof_record(None, fam, {}, "none") is None
 
 
+def test_detail_table_needs_the_full_run():
+    """--detail comes from the profiled step of --full: without it the command line is refused before any GPU work"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail", "x.txt"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 2 and "--detail needs --full" in r.stderr
+
+
 def test_pmc_traffic_maps_kernel_names_onto_the_bench_families():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pmc_traffic as pt

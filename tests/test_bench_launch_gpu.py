@@ -18,7 +18,7 @@ def _run(extra, env_extra):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VLFB_BENCH_CHILD", "VLFB_DIST_FORCE"):
         env.pop(k, None)
     env.update(env_extra)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--clips-per-gpu", "1", "--frames", "16",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--clips-per-gpu", "1", "--frames", "16",
            "--crop", "64", "--no-cpu-baseline", "--no-fp32-line", "--no-split-line", "--no-fp16-line"] + extra
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     return r

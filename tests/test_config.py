@@ -1,12 +1,24 @@
 """core.config keeps the reference's surface: strict YAML merge, KEY VAL overrides, derived keys;
-the presets equal the reference's configs/*.yaml (checked where /root/reference is mounted)."""
-import glob
+the presets equal the reference's configs/*.yaml (their text is the fixture tests/golden/ref_configs.json.gz, made by
+oracle/make_ref_config_golden.py)."""
+import gzip
 import json
 import os
 
 import pytest
 
-REF = "/root/reference/configs"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_configs.json.gz")
+
+
+@pytest.fixture(scope="module")
+def ref_configs(tmp_path_factory):
+    """the reference's configs/*.yaml, written out unmodified into a directory of their own"""
+    with gzip.open(GOLDEN, "rb") as fh:
+        yamls = json.loads(fh.read().decode())["yamls"]
+    d = tmp_path_factory.mktemp("configs")
+    for name, text in yamls.items():
+        (d / name).write_bytes(text.encode("utf-8"))
+    return str(d)
 
 
 def _tree(cfg):
@@ -38,10 +50,9 @@ def test_strict_merge_rules():
     C.reset_cfg()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-def test_every_reference_yaml_loads_unmodified():
+def test_every_reference_yaml_loads_unmodified(ref_configs):
     from core import config as C
-    files = sorted(glob.glob(os.path.join(REF, "*.yaml")))
+    files = sorted(os.path.join(ref_configs, f) for f in os.listdir(ref_configs) if f.endswith(".yaml"))
     assert len(files) == 26
     for f in files:
         C.reset_cfg()
@@ -51,15 +62,14 @@ def test_every_reference_yaml_loads_unmodified():
     C.reset_cfg()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-def test_presets_equal_the_reference_yamls():
+def test_presets_equal_the_reference_yamls(ref_configs):
     from core import config as C
     from vlfb.presets import PRESETS, load_preset
     for name in PRESETS:
         load_preset(name)
         mine = _tree(C.config)
         C.reset_cfg()
-        C.cfg_from_file(os.path.join(REF, name + ".yaml"))
+        C.cfg_from_file(os.path.join(ref_configs, name + ".yaml"))
         C.assert_and_infer_cfg()
         assert mine == _tree(C.config), name
     C.reset_cfg()

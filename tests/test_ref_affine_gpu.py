@@ -1,22 +1,25 @@
 """AffineNd pinned against REFERENCE-BUILT code: oracle/_ref/libref_affine_nd.so is the reference's own
 caffe2_customized_ops/video/affine_nd_op.cu (kernels :31-58 and both RunOnDevice bodies :61-107)
-compiled unmodified by oracle/build_ref.py.  Checked here:
+compiled unmodified by oracle/build_ref.py; what it computes on the seeded inputs of every shape below is committed as
+SHA-256 digests of its outputs (tests/golden/ref_affine_nd.json, oracle/make_ref_affine_golden.py).  Checked here:
   * vlfb_affine_nd_fwd / vlfb_affine_nd_bwd (the drop-in operator of include/vlfb.h) == the reference
-    operator, BIT-EXACT (fp32, same fma contraction),
+    operator, BIT-EXACT (fp32, same fma contraction): equal digests,
   * the CPU oracle's `_affine` restatement == the reference operator to 1 ulp (torch-CPU rounds the
     product before the add, the GPU build fuses it), and its fp64 form to fp32 round-off.
-The library is test infrastructure: only tests/ load it."""
+The library is test infrastructure: only tests/ and the fixture generator load it."""
 import ctypes as C
+import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from oracle.make_ref_affine_golden import SHAPES, digest, inputs, key
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_affine_nd.so")
-
-SHAPES = [(2, 64, 8 * 14 * 14), (1, 256, 4 * 7 * 7), (3, 2048, 1), (2, 3, 5), (1, 1, 4099), (4, 512, 16 * 7 * 7 + 3)]
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_affine_nd.json")
 
 
 def _ref():
@@ -44,24 +47,19 @@ def test_affine_nd_matches_the_reference_built_operator_bit_exactly(shape):
     from vlfb import hip
     from oracle import model as om
     n, c, inner = shape
-    g = torch.Generator().manual_seed(1234 + n * 7 + c)
-    x = torch.randn(n, c, inner, generator=g)
-    s = torch.rand(c, generator=g) + 0.5
-    b = torch.randn(c, generator=g) * 0.1
+    x, s, b = inputs(shape)
+    with open(GOLDEN) as fh:
+        want = json.load(fh)["cases"][key(shape)]
+    assert digest(x, s, b) == want["inputs"], "the seeded inputs differ from those the fixture was made from"
     xd, sd, bd = x.cuda(), s.cuda(), b.cuda()
-    ref = _ref()
-    stream = torch.cuda.current_stream().cuda_stream
-    y_ref = torch.full_like(xd, float("nan"))
-    assert ref.ref_affine_nd_fwd(xd.data_ptr(), sd.data_ptr(), bd.data_ptr(), y_ref.data_ptr(), n, c, inner, stream) == 0
     y = torch.full_like(xd, float("nan"))
     hip.call("vlfb_affine_nd_fwd", hip.ptr(xd), hip.ptr(sd), hip.ptr(bd), hip.ptr(y), n, c, inner)
-    dx_ref = torch.full_like(xd, float("nan"))
-    assert ref.ref_affine_nd_bwd(xd.data_ptr(), sd.data_ptr(), dx_ref.data_ptr(), n, c, inner, stream) == 0
     dx = torch.full_like(xd, float("nan"))
     hip.call("vlfb_affine_nd_bwd", hip.ptr(xd), hip.ptr(sd), hip.ptr(dx), n, c, inner)
     torch.cuda.synchronize()
-    assert torch.equal(y, y_ref), "vlfb_affine_nd_fwd differs from the reference-built AffineNdOp"
-    assert torch.equal(dx, dx_ref), "vlfb_affine_nd_bwd differs from the reference-built AffineNdGradientOp"
+    assert digest(y) == want["y"], "vlfb_affine_nd_fwd differs from the reference-built AffineNdOp"
+    assert digest(dx) == want["dx"], "vlfb_affine_nd_bwd differs from the reference-built AffineNdGradientOp"
+    y_ref = y         # (bit for bit the reference operator's output, by the digest)
     # the oracle's restatement (what every model-level parity test leans on)
     P = {"p_s": s, "p_b": b}
     y_or = om._affine(x.view(n, c, inner, 1, 1), P, "p").view(n, c, inner)
