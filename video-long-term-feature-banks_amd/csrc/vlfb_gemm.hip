@@ -1548,7 +1548,6 @@ static int conv_run_impl(const vlfb_conv_desc* d, const void* A, const void* B, 
   g.dbias = pl.bias_fused ? dbias : nullptr;
   g.R2 = (const char*)R_lo; g.O2 = (char*)O_lo;
   g.pair_io = sp_pair ? 1 : 0;
-  g.pair_il = (pl.h2 && d->a_pstride == 32) ? 1 : 0;
   // Non-temporal epilogue rows (GP::nt_epi) where a launch moves at least 4 bytes per output element through its epilogue
   // -- fp32 or two-plane outputs / residuals, two-term gradients: the "mix" and "split" launches, +1.0-1.3 % on their steps --
   // and not on plain 16-bit launches, whose steps measured -0.25 % with it (their rows are half as large, the next launch

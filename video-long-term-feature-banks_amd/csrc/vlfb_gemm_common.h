@@ -58,8 +58,6 @@ struct GP {
   // split-bf16 NT launches (vlfb_gemm_split.hip) with a TWO-PLANE fp16 output: O / O2 and R / R2 are fp16 planes (hi, lo)
   // instead of fp32 tensors -- where an fp32 operand (the attention output of a non-local block) enters the two-plane forward
   int pair_io;
-  // VLFB_MATH_F16X3: the two planes INTERLEAVED in groups of 32 k ([row][k / 32][hi 32 | lo 32]; a_ps = b_ps = 32 elements)
-  int pair_il;
   // epilogue traffic -- output rows, residual and mask rows: touched once per launch -- with the non-temporal hint, so that
   // it streams through the L2 instead of evicting the operand panels the other workgroups of the XCD are re-reading
   // (set per launch in conv_run_impl, VLFB_NT_EPI; measured per launch and in the step)

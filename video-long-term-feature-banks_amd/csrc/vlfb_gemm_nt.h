@@ -114,9 +114,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
   // PAIR: chunk ccg of a row = 16 bytes at k-offset (ccg & 3) * 8 of plane ccg >> 2
   const unsigned a_cb = PAIR ? (unsigned)(ccg & 3) * 16u + (unsigned)(ccg >> 2) * (unsigned)p.a_ps * 2u : (unsigned)(ccg * EPC) * (unsigned)sizeof(T);
   const unsigned b_cb = PAIR ? (unsigned)(ccg & 3) * 16u + (unsigned)(ccg >> 2) * (unsigned)p.b_ps * 2u : (unsigned)(ccg * EPC) * (unsigned)sizeof(T);
-  // bytes a k-tile advances along a row: planes layout = 32 k of each plane (64 bytes); interleaved layout (GP::pair_il: rows of
-  // [32 k of hi | the same 32 k of lo] groups, a_ps = b_ps = 32) = one whole 128-byte group
-  const int KTB = PAIR ? (p.pair_il ? RB : RB / 2) : RB;
+  // bytes a k-tile advances along a row (PAIR: 32 k of each plane, 64 bytes)
+  const int KTB = PAIR ? RB / 2 : RB;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
   RowC arow[A_IT];
@@ -200,7 +199,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
       if (UT) {
         const int sgn = DGRAD ? -1 : 1;
         const int da = sgn * u_a * p.dt, db = sgn * u_b * p.dh, dc = sgn * u_c * p.dw;   // scalar
-        const unsigned dbyte = (unsigned)(((da * p.Hs + db) * p.Ws + dc) * p.lda + ((PAIR && p.pair_il) ? 2 * u_ci : u_ci)) * (unsigned)sizeof(T);
+        const unsigned dbyte = (unsigned)(((da * p.Hs + db) * p.Ws + dc) * p.lda + u_ci) * (unsigned)sizeof(T);
         if (!W2I || !(kt_seq & 1)) {
 #pragma unroll
           for (int i = 0; i < A_IT; ++i) {
