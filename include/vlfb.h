@@ -213,8 +213,10 @@ int vlfb_conv_plan_describe(const vlfb_conv_desc* d, char* buf, int64_t buf_byte
  *   VLFB_WS_FBO_ATTN_BWD   arg = const int64_t[2] {r, k}          `ds_ws` of vlfb_fbo_attn_bwd (r RoIs x k bank rows, fp32)
  *   VLFB_WS_ATTN_SCORES    arg = const int64_t[3] {b, l1, l2}     fp32 score matrix between the scores GEMM and
  *                                                                vlfb_softmax_fwd / _bwd when the fused kernels are not used
- *   VLFB_WS_BN             arg = const int64_t[3] {dtype, rows, C} `workspace` of vlfb_bn_fwd / _bwd (= vlfb_bn_workspace_bytes) */
-enum { VLFB_WS_CONV = 0, VLFB_WS_MAXPOOL_ARGMAX = 1, VLFB_WS_FBO_ATTN_BWD = 2, VLFB_WS_ATTN_SCORES = 3, VLFB_WS_BN = 4 };
+ *   VLFB_WS_BN             arg = const int64_t[3] {dtype, rows, C} `workspace` of vlfb_bn_fwd / _bwd (= vlfb_bn_workspace_bytes)
+ *   VLFB_WS_CLASS_AP       arg = const int64_t[2] {n, cols}       `workspace` of vlfb_class_ap_auc (its global sort path) */
+enum { VLFB_WS_CONV = 0, VLFB_WS_MAXPOOL_ARGMAX = 1, VLFB_WS_FBO_ATTN_BWD = 2, VLFB_WS_ATTN_SCORES = 3, VLFB_WS_BN = 4,
+       VLFB_WS_CLASS_AP = 5 };
 int64_t vlfb_query_workspace(int op, const void* arg);
 /* A: activation / gradient operand; B: weight operand (FPROP/DGRAD) or unused (WGRAD);
  * P: WGRAD output-gradient operand; O: output; bias/rowscale: fp32 vectors or NULL;
@@ -591,6 +593,53 @@ typedef struct vlfb_clip_desc {
 int vlfb_clip_preprocess(const vlfb_clip_desc* d, const uint8_t* frames, const int32_t* xofs,
                          const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, void* dst,
                          int dst_dtype, vlfb_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Evaluation metrics on the device.  Replace the host meter of lib/utils/metrics.py, which fetches `pred` and
+ * `labels` from every GPU every iteration (get_multi_gpu_outputs, :514-540), and tools/evaluate_actions.py.
+ * All state (counters, cursor, tables) is caller-owned device memory; every count is an integer and the two
+ * floating-point sums are taken in a fixed order, so results do not depend on the launch geometry.
+ * ------------------------------------------------------------------------------------------ */
+/* Top-k hits of single-label heads (compute_topk_correct_hits, metrics.py:485-500; compute_top_k_verbs_or_nouns,
+ * evaluate_actions.py:63-74).  scores [rows][cols] (`dtype`), labels [rows], ks: nk <= 4 HOST values, 1 <= k <= cols.
+ * ADDS into hits [nk + 1]: hits per k, and in the last slot the number of rows counted.  A row with label < 0 or
+ * >= cols is skipped.  rank = #{j : s_j > s_label} + #{j < label : s_j == s_label}; hit iff rank < k; a row whose
+ * label score is NaN is a counted miss.  (The reference's two argsort spellings disagree on ties and numpy's default
+ * sort is not stable: ties are pinned by this rule.) */
+int vlfb_topk_hits(const void* scores, int dtype, const int32_t* labels, int64_t rows, int64_t cols, const int32_t* ks,
+                   int nk, int64_t* hits, vlfb_stream_t stream);
+/* EPIC action top-k (compute_top_k_actions, evaluate_actions.py:77-98): the same rank rule over the flattened index
+ * v * Nn + n of (verb[r][v] * noun[r][n]) * prior[v][n], each product rounded to fp32 in that order; prior may be NULL.
+ * A row with either label out of range is skipped. */
+int vlfb_action_topk_hits(const float* verb, const float* noun, const float* prior, const int32_t* verb_labels,
+                          const int32_t* noun_labels, int64_t rows, int64_t V, int64_t Nn, const int32_t* ks, int nk,
+                          int64_t* hits, vlfb_stream_t stream);
+/* Clip merge (aggregate_predictions_from_clips, metrics.py:165-186; all_preds.append, :384-388) while the clips
+ * arrive: row r of the call goes to item (cursor + r) % n_items of table fp32 [n_items][cols] / table_labels uint8
+ * [n_items][cols]; the element-wise result is max(table, row) (a NaN score leaves the table as it is), rows of one call
+ * that land on one item included.  `cursor` is an int64 IN DEVICE MEMORY that the call reads and then advances by
+ * `rows`, so the call can sit in a replayed call list or a captured graph with constant arguments.  total_rows > 0:
+ * rows at stream positions >= total_rows are dropped (stack_predictions, :143-163, cuts the padding of the last
+ * batch).  The caller fills the table with -inf and table_labels with 255 (= not visited); labels (int32 [rows][cols],
+ * > 0 = positive) of a revisited item that differ from what is there are COUNTED, per element, into *mismatches
+ * (the reference asserts, :178-181). */
+int vlfb_scores_merge_max(const void* scores, int dtype, const int32_t* labels, int64_t rows, int64_t cols, float* table,
+                          uint8_t* table_labels, int64_t n_items, int64_t total_rows, int64_t* cursor,
+                          int32_t* mismatches, vlfb_stream_t stream);
+/* Per class c of table [n][cols] / table_labels: average precision and ROC-AUC in fp64 and the number of positives
+ * (sklearn.metrics.average_precision_score / roc_auc_score as mean_ap_metric calls them, metrics.py:444-482), ties
+ * grouped: the column sorted descending, e_g = last index of the g-th run of equal scores, tp_g = positives in
+ * [0, e_g], P = tp_last, fp_g = e_g + 1 - tp_g:
+ *   AP  = sum_g (tp_g - tp_{g-1}) * tp_g / (P * (e_g + 1))
+ *   AUC = sum_g (fp_g - fp_{g-1}) * (tp_g + tp_{g-1}) / (2 * P * (n - P))
+ * (integer numerators and denominators, one division per term).  P == 0: AP = AUC = NaN; P == n: AUC = NaN.
+ * n <= 8192: the column is sorted in LDS and `workspace` is not used; above that, or with VLFB_CLASS_AP_FORCE_GLOBAL
+ * in `flags`, the same network runs over `workspace` (vlfb_query_workspace(VLFB_WS_CLASS_AP, {n, cols}) bytes).  Both
+ * paths give bit-identical results. */
+#define VLFB_CLASS_AP_MAX_N (1 << 20)
+enum { VLFB_CLASS_AP_FORCE_GLOBAL = 1 };
+int vlfb_class_ap_auc(const float* table, const uint8_t* table_labels, int64_t n, int64_t cols, double* ap, double* auc,
+                      int32_t* n_pos, void* workspace, int64_t workspace_bytes, int flags, vlfb_stream_t stream);
 
 #ifdef __cplusplus
 }

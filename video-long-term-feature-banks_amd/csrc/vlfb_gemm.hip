@@ -1441,6 +1441,7 @@ extern "C" int vlfb_conv_plan_describe(const vlfb_conv_desc* d, char* buf, int64
   return VLFB_OK;
 }
 
+int64_t vlfb_class_ap_workspace_bytes_impl(int64_t n, int64_t cols);   // vlfb_metrics.hip
 extern "C" int64_t vlfb_query_workspace(int op, const void* arg) {
   if (!arg) { set_error(VLFB_ERR_ARG, "query_workspace: arg is required"); return -1; }
   switch (op) {
@@ -1465,6 +1466,12 @@ extern "C" int64_t vlfb_query_workspace(int op, const void* arg) {
       const int64_t* v = static_cast<const int64_t*>(arg);
       const int64_t n = vlfb_bn_workspace_bytes((int)v[0], v[1], v[2]);
       if (n < 0) set_error(VLFB_ERR_ARG, "query_workspace: bad dtype / rows / C for SpatialBN");
+      return n;
+    }
+    case VLFB_WS_CLASS_AP: {
+      const int64_t* v = static_cast<const int64_t*>(arg);
+      const int64_t n = vlfb_class_ap_workspace_bytes_impl(v[0], v[1]);
+      if (n < 0) set_error(VLFB_ERR_ARG, "query_workspace: class_ap needs 1 <= n <= %d and cols >= 1", VLFB_CLASS_AP_MAX_N);
       return n;
     }
     default: set_error(VLFB_ERR_ARG, "query_workspace: unknown op %d", op); return -1;

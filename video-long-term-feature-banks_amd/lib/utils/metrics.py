@@ -1,0 +1,230 @@
+"""The reference's lib/utils/metrics.py -- import path and names -- on device-resident counters.
+
+The reference's meter fetches `pred` and `labels` from every GPU every iteration (get_multi_gpu_outputs, :514-540)
+and calls scikit-learn at the end.  Here the numbers are accumulated by kernels inside the step
+(vlfb.metrics.DeviceMeter, attached with Engine.attach_meter) and read once per cfg.LOG_PERIOD; mAP / wAP / ROC-AUC
+come from vlfb_class_ap_auc.
+
+Differences that follow from reading once per period:
+  * `top1` / `top5` of a log line are the error over the iterations since the previous line (the reference prints the
+    last iteration's); the aggregated figures are the reference's (every iteration has the same batch size).
+  * `Loss` is the last iteration's, from the engine's device loss ring.
+AVA's frame-mAP is absent: the reference does not ship the evaluator utils/ava_eval_helper.py imports
+(utils.ava_evaluation.*), so finalize_metrics raises NotImplementedError for cfg.DATASET == 'ava'.
+"""
+from __future__ import absolute_import, division, print_function, unicode_literals
+
+import datetime
+import logging
+
+import numpy as np
+import torch
+
+from core.config import config as cfg
+from vlfb import dist
+from vlfb.metrics import DeviceMeter
+
+logger = logging.getLogger(__name__)
+
+
+def _dev(x, dtype):
+    if isinstance(x, torch.Tensor):
+        t = x.to(device="cuda", dtype=dtype if dtype is not None else x.dtype)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(x))).to(device="cuda", dtype=dtype)
+    return t.contiguous()
+
+
+def _scores(x):
+    if isinstance(x, torch.Tensor) and x.dtype in (torch.float16, torch.bfloat16):
+        return _dev(x, None)
+    return _dev(x, torch.float32)
+
+
+def compute_topk_correct_hits(top_k, preds, labels):
+    """number of rows whose label is among the top_k scores (metrics.py:485-500); numpy arrays or device tensors.
+    Ties follow the rank rule of include/vlfb.h (vlfb_topk_hits)."""
+    preds = _scores(preds)
+    preds = preds.reshape(preds.shape[0], -1)
+    meter = DeviceMeter("topk", preds.shape[1], ks=(top_k,), device=preds.device)
+    meter.update(preds, _dev(labels, torch.int32).reshape(-1))
+    return meter.read()["hits"][int(top_k)]
+
+
+def mean_ap_metric(predicts, targets):
+    """(mean_auc, mean_ap, mean_wap, all_aps) for Charades (metrics.py:444-482) without scikit-learn; numpy arrays,
+    lists of them, or device tensors"""
+    if isinstance(predicts, (list, tuple)):
+        predicts = torch.cat([_scores(p) for p in predicts]) if isinstance(predicts[0], torch.Tensor) else np.vstack(predicts)
+        targets = torch.cat([_dev(t, torch.int32) for t in targets]) if isinstance(targets[0], torch.Tensor) else np.vstack(targets)
+    predicts, targets = _scores(predicts), _dev(targets, torch.int32)
+    logger.info("Getting mAP for {} examples".format(predicts.shape[0]))
+    meter = DeviceMeter("map", predicts.shape[1], n_items=predicts.shape[0], device=predicts.device)
+    meter.update(predicts, targets)
+    r = meter.read()
+    return r["mean_auc"], r["mean_ap"], r["mean_wap"], r["all_aps"]
+
+
+class MetricsCalculator(object):
+    """MetricsCalculator(engine, split): owns the DeviceMeter of the engine's head and attaches it.  `model` of the
+    reference's signature is the planned vlfb.engine.Engine here; `test_labels` is the int32 device tensor a
+    test-mode net (no label blob) is metered against (Engine.attach_meter)."""
+
+    def __init__(self, engine, split, video_idx_to_name=None, total_num_boxes=None, test_labels=None):
+        self.model = self.engine = engine
+        self.split = split
+        self.video_idx_to_name = video_idx_to_name
+        self._total_num_boxes = total_num_boxes
+        self.best_top1 = float('inf')
+        self.best_top5 = float('inf')
+        self.best_map = float('inf') * (-1.0)
+        self.lr = 0
+        self.num_test_clips = 1
+        if cfg.DATASET == 'charades':
+            # (tools/test_net.py / train_net.py set NUM_TEST_CLIPS from _FINAL_EVAL / _DURING_TRAINING before they test)
+            self.num_test_clips = cfg.CHARADES.get("NUM_TEST_CLIPS", cfg.CHARADES.NUM_TEST_CLIPS_DURING_TRAINING)
+        self.meter = None
+        from vlfb.engine import LossStep
+        heads = [st for st in engine.steps if isinstance(st, LossStep) and st.prob is not None]
+        if cfg.DATASET != 'ava' and heads:
+            cols, self.batch_rows = heads[0].cols, heads[0].rows
+            if cfg.MODEL.MULTI_LABEL:
+                if split != 'train':                 # (the reference computes no mAP while training: full_map = 0)
+                    total = self.num_test_clips * cfg.TEST.DATASET_SIZE // dist.world_size()
+                    self.meter = DeviceMeter("map", cols, n_items=max(total // self.num_test_clips, 1), total_rows=total,
+                                             device=engine.device)
+            else:
+                self.meter = DeviceMeter("topk", cols, ks=(1, 5), device=engine.device)
+            if self.meter is not None:
+                engine.attach_meter(self.meter, labels=test_labels)
+        self.reset()
+
+    def reset(self):
+        logger.info('Resetting {} metrics...'.format(self.split))
+        self.aggr_loss = 0.0
+        self.aggr_batch_size = 0
+        self._last = (0, 0, 0)                       # hits@1, hits@5, rows at the previous read
+        self.avg_loss = self.avg_err = self.avg_err5 = float('nan')
+        self.full_map = 0.0
+        if self.meter is not None:
+            self.meter.reset()
+
+    def _read_topk(self):
+        """(period err, period err5, aggregated err, aggregated err5) from ONE read, summed over ranks"""
+        own_hits, rows, _, _ = self.meter.counters()
+        h1, h5, rows = dist.sum_ints(own_hits + [rows], self.engine.device)
+        p1, p5, prow = h1 - self._last[0], h5 - self._last[1], rows - self._last[2]
+        self._last = (h1, h5, rows)
+        err = lambda h, n: (1.0 - float(h) / n) * 100 if n else float('nan')
+        self.avg_err, self.avg_err5 = err(h1, rows), err(h5, rows)
+        self.aggr_batch_size = rows
+        return err(p1, prow), err(p5, prow), self.avg_err, self.avg_err5
+
+    def calculate_and_log_all_metrics_train(self, curr_iter, timer, suffix=''):
+        if (curr_iter + 1) % cfg.LOG_PERIOD != 0:
+            return
+        self.lr = float(self.engine.lr)
+        losses = self.engine.recent_losses()
+        cur_loss = losses[-1] if losses else float('nan')
+        if losses:
+            self.aggr_loss += float(np.sum(losses))
+            self._loss_count = getattr(self, "_loss_count", 0) + len(losses)
+            self.avg_loss = self.aggr_loss / self._loss_count
+        rem_iters = cfg.SOLVER.MAX_ITER - curr_iter - 1
+        eta = str(datetime.timedelta(seconds=int(timer.average_time * rem_iters)))
+        epoch = (curr_iter + 1) / (cfg.TRAIN.DATASET_SIZE / cfg.TRAIN.BATCH_SIZE)
+        log_str = ' '.join((
+            '| Train ETA: {} LR: {:.8f}',
+            ' Iters [{}/{}]',
+            '[{:.2f}ep]',
+            ' Time {:0.3f}',
+            ' Loss {:7.4f}',
+        )).format(eta, self.lr, curr_iter + 1, cfg.SOLVER.MAX_ITER, epoch, timer.diff, cur_loss)
+        if not cfg.MODEL.MULTI_LABEL and self.meter is not None:
+            cur_err, cur_err5, _, _ = self._read_topk()
+            log_str += ' top1 {:7.3f} top5 {:7.3f}'.format(cur_err, cur_err5)
+        print(log_str)
+
+    def calculate_and_log_all_metrics_test(self, curr_iter, timer, total_iters, suffix=''):
+        cur_batch_size = self.batch_rows * dist.world_size() if self.meter is not None else 0
+        if cfg.MODEL.MULTI_LABEL:
+            self.aggr_batch_size += cur_batch_size
+        if (curr_iter + 1) % cfg.LOG_PERIOD == 0 or curr_iter + 1 == total_iters:
+            tail = ''
+            if not cfg.MODEL.MULTI_LABEL and self.meter is not None:
+                cur_err, cur_err5, avg_err, avg_err5 = self._read_topk()
+                tail = (' top1 {:7.3f} ({:7.3f})' + '  top5 {:7.3f} ({:7.3f})').format(cur_err, avg_err, cur_err5, avg_err5)
+            test_str = ' '.join((
+                '| Test: [{}/{}]',
+                ' Time {:0.3f}',
+                ' current batch {}',
+                ' aggregated batch {}',
+            )).format(curr_iter + 1, total_iters, timer.diff, cur_batch_size, self.aggr_batch_size)
+            print(test_str + tail)
+
+    def finalize_metrics(self, is_train=False, name='latest'):
+        """the final figures: mAP of the merged table (Charades), or the aggregated top-1 / top-5 error"""
+        if cfg.DATASET == 'ava':
+            raise NotImplementedError(
+                "AVA frame-mAP: the reference does not ship its evaluator (utils/ava_eval_helper.py imports "
+                "utils.ava_evaluation.*, which is absent), so there is nothing to compute it with")
+        if self.meter is None:
+            self.full_map = 0.0
+            return
+        if cfg.MODEL.MULTI_LABEL:
+            if is_train:
+                self.full_map = 0.0
+                return
+            _, _, cursor, mismatches = self.meter.counters()
+            n = self.meter.filled(cursor)
+            assert mismatches == 0, "labels of %d merged clip elements differ from their video's" % mismatches
+            if dist.world_size() > 1:
+                # every rank holds the videos it tested: gather the tables once and score them together
+                table = dist.gather_rows(self.meter.table[:n])
+                labels = dist.gather_rows(self.meter.labels[:n])
+                self.full_map = mean_ap_metric(table, labels.to(torch.int32))[1]
+            else:
+                self.results = self.meter.read()
+                self.full_map = self.results["mean_ap"]
+        else:
+            self._read_topk()
+
+    def get_computed_metrics(self):
+        json_stats = {}
+        if cfg.MODEL.MULTI_LABEL:
+            if self.split == 'train':
+                json_stats['train_loss'] = self.avg_loss
+                json_stats['train_full_map'] = self.full_map
+            elif self.split in ['test', 'val']:
+                json_stats['test_full_map'] = self.full_map
+                json_stats['test_best_map'] = self.best_map
+        else:
+            if self.split == 'train':
+                json_stats['train_loss'] = self.avg_loss
+                json_stats['train_err'] = self.avg_err
+                json_stats['train_err5'] = self.avg_err5
+            elif self.split in ['test', 'val']:
+                json_stats['test_err'] = self.avg_err
+                json_stats['test_err5'] = self.avg_err5
+                json_stats['best_err'] = self.best_top1
+                json_stats['best_err5'] = self.best_top5
+        return json_stats
+
+    def log_final_metrics(self, model_iter, total_iters=None):
+        if total_iters is None:
+            total_iters = cfg.SOLVER.MAX_ITER
+        if cfg.MODEL.MULTI_LABEL:
+            print('* {} testing finished #iters [{}|{}]: mAP: {:.3f}'.format('', model_iter + 1, total_iters, self.full_map))
+        else:
+            print('* Finished #iters [{}|{}]: top1: {:.3f} top5: {:.3f}'.format(
+                model_iter + 1, total_iters, 100.0 - self.avg_err, 100.0 - self.avg_err5))
+
+    def compute_and_log_best(self):
+        if cfg.MODEL.MULTI_LABEL:
+            if self.full_map > self.best_map:
+                self.best_map = self.full_map
+                print('\n* Best model: mAP: {:7.3f}\n'.format(self.best_map))
+        elif self.avg_err < self.best_top1:
+            self.best_top1 = self.avg_err
+            self.best_top5 = self.avg_err5
+            print('\n* Best model: top1: {:7.3f} top5: {:7.3f}\n'.format(self.best_top1, self.best_top5))

@@ -64,3 +64,25 @@ def all_ok(flag):
     t = torch.tensor([1 if flag else 0], device=dev, dtype=torch.int32)
     td.all_reduce(t, op=td.ReduceOp.MIN)
     return bool(int(t.item()))
+
+
+def sum_ints(values, device=None):
+    """element-wise sum of a list of Python ints over all ranks (the meter's hit / row counters); the list itself
+    without a group"""
+    values = [int(v) for v in values]
+    if not initialized():
+        return values
+    dev = device if td.get_backend() == "nccl" else "cpu"
+    t = torch.tensor(values, device=dev, dtype=torch.int64)
+    td.all_reduce(t, op=td.ReduceOp.SUM)
+    return [int(v) for v in t.cpu().tolist()]
+
+
+def gather_rows(t):
+    """rows of every rank's 2-D tensor (the same number on each), concatenated in rank order; `t` without a group"""
+    if not initialized():
+        return t
+    src = t.contiguous() if td.get_backend() == "nccl" else t.cpu().contiguous()
+    parts = [torch.empty_like(src) for _ in range(world_size())]
+    td.all_gather(parts, src)
+    return torch.cat(parts).to(t.device)

@@ -1396,6 +1396,10 @@ class LossStep(Step):
                  self.scale)
         if self.dlogits is not None and self.eng.loss_scale != 1.0:
             hip.call("vlfb_scale_inplace", hip.ptr(self.dlogits), self.dlogits.numel(), self.eng.loss_scale)
+        if self.eng.meter is not None and self.prob is not None:
+            # device-side metrics (Engine.attach_meter): constant arguments, so the calls are recorded / captured with the step
+            labels = self.labels.ptr() if self.labels is not None else hip.ptr(self.eng.meter_labels)
+            self.eng.meter.update_ptr(self.prob.ptr(), hip.F32, labels, self.rows)
         if not self.eng._dev_scalars:  # (a captured step pushes after the replay: the ring position is host state)
             self.ring_push()
 
@@ -1960,6 +1964,8 @@ class Engine(object):
         self._graph_stream = None
         self._eager_steps = 0
         self._trace = None             # recorded step (STEP_TRACE)
+        self.meter = None              # vlfb.metrics.DeviceMeter fed behind every loss head (attach_meter)
+        self.meter_labels = None
         self._wq = []                  # parameter-gradient launches waiting for their lag (WGRAD_LAG)
         self._bwd_index = 0
         self._trace_key = None
@@ -3149,6 +3155,33 @@ class Engine(object):
             self._plan_solver_buckets(bucket_mb)
         self.comm = GradComm(self.flat_grad, None, int(bucket_mb) << 20,
                              buckets=[(b["start"], b["end"], b["ready"]) for b in self.sol_buckets])
+
+    def attach_meter(self, meter, labels=None):
+        """Feed `meter` (vlfb.metrics.DeviceMeter; None detaches) with the probability blob and the label blob of every
+        loss head, on the main stream right behind the head's kernel -- what the reference's meter fetches to the host
+        every iteration (lib/utils/metrics.py:514-540).  The head of a test-mode net reads no labels: they are taken from the fed
+        `labels*` input blob, or from `labels`, an int32 device tensor ([rows] class indices / [rows][classes] multi-hot) the
+        caller refills before every forward pass.
+        The meter only reads the step's blobs; a recorded / captured step is re-recorded with (or without) its calls."""
+        heads = [st for st in self.steps if isinstance(st, LossStep) and st.prob is not None]
+        if meter is not None:
+            if not heads:
+                raise hip.VlfbError("attach_meter: the planned net has no head that produces probabilities")
+            for st in heads:
+                want = "topk" if st.kernel == "vlfb_softmax_ce" else "map"
+                if meter.kind != want or meter.cols != st.cols:
+                    raise hip.VlfbError("attach_meter: a %r meter of %d classes on a %s head of %d classes (needs %r)" % (
+                        meter.kind, meter.cols, st.kernel, st.cols, want))
+                if st.labels is None:
+                    n = st.rows * (1 if want == "topk" else st.cols)
+                    if labels is None:               # the fed `labels*` input blob nothing in a test-mode graph reads
+                        fed = [b for k, b in self.env.items() if str(k).startswith("labels") and b.root.tensor is not None]
+                        labels = fed[0].root.tensor if len(fed) == 1 else None
+                    if labels is None or labels.dtype != torch.int32 or labels.numel() != n or not labels.is_contiguous():
+                        raise hip.VlfbError("attach_meter: the head has no label blob; pass `labels`, a contiguous int32 device "
+                                            "tensor of %d elements" % n)
+        self.meter, self.meter_labels = meter, (labels if meter is not None else None)
+        self._trace = self._graph = None
 
     def recent_losses(self):
         """losses since the last call (device ring of the loss step; a single host sync)"""

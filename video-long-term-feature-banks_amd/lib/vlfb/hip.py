@@ -174,6 +174,10 @@ _SIGS = {
     "vlfb_lfb_gather_slots": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _P, _I64, C.c_int, C.c_int, _P, C.c_int, _P]),
     "vlfb_lfb_sample_compact": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, _P, C.c_int, _P]),
     "vlfb_lfb_sample_packed": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "vlfb_topk_hits": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, C.c_int, _P, _P]),
+    "vlfb_action_topk_hits": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, C.c_int, _P, _P]),
+    "vlfb_scores_merge_max": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P]),
+    "vlfb_class_ap_auc": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, C.c_int, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
@@ -291,7 +295,9 @@ def conv_plan(d):
     return buf.value.decode()
 
 
-WS_CONV, WS_MAXPOOL_ARGMAX, WS_FBO_ATTN_BWD, WS_ATTN_SCORES, WS_BN = 0, 1, 2, 3, 4
+WS_CONV, WS_MAXPOOL_ARGMAX, WS_FBO_ATTN_BWD, WS_ATTN_SCORES, WS_BN, WS_CLASS_AP = 0, 1, 2, 3, 4, 5
+CLASS_AP_FORCE_GLOBAL = 1                           # vlfb_class_ap_auc flags: sort in the global workspace whatever n is
+CLASS_AP_LDS_MAX = 8192                             # largest n vlfb_class_ap_auc sorts in LDS
 
 
 def query_workspace(op, arg):
@@ -399,3 +405,9 @@ def pool_desc(dtype, N, Ti, Hi, Wi, Cc, To, Ho, Wo, k, s, p):
     d.st, d.sh, d.sw = s
     d.pt, d.ph, d.pw = p
     return d
+
+
+def ks_array(ks):
+    """the HOST array of k values vlfb_topk_hits / vlfb_action_topk_hits read (a recorded call keeps it alive)"""
+    ks = [int(k) for k in ks]
+    return C.cast((C.c_int32 * max(len(ks), 1))(*ks), C.c_void_p), len(ks)

@@ -1,0 +1,160 @@
+"""Evaluation metrics accumulated on the device (csrc/vlfb_metrics.hip).
+
+The reference's meter (lib/utils/metrics.py) fetches `pred` and `labels` from every GPU every iteration.  A step of
+this engine is a replayed call list or a captured graph that never synchronises, so the meter is a set of kernels with
+constant arguments that sit inside the step and add into device state; `read()` is the one call that synchronises.
+
+  kind "topk"  single-label heads (EPIC verbs / nouns): hits for every k of `ks` and the number of rows counted
+  kind "map"   multi-label heads (Charades): a score table [n_items][cols] into which every prediction row is merged by
+               max at (stream position % n_items) -- clip c of video i arrives at position i + c * n_items, which is
+               aggregate_predictions_from_clips (metrics.py:165-186) done while the clips arrive -- and from which
+               `read()` computes mAP / wAP / ROC-AUC (mean_ap_metric, :444-482)
+
+Tie rule of top-k: rank = #{j : s_j > s_label} + #{j < label : s_j == s_label}, hit iff rank < k (include/vlfb.h).
+"""
+import numpy as np
+import torch
+
+from vlfb import hip
+
+
+def _align(n, a=256):
+    return (n + a - 1) // a * a
+
+
+def summarize_ap(ap, auc, n_pos):
+    """mean_ap_metric's reductions (metrics.py:453-480) from per-class AP / AUC / positives: classes without a positive
+    are dropped from the means and get 0 in all_aps; mean_wap weights by positives; mean_auc is the plain mean over the
+    kept classes, NaN as soon as one of them is all-positive (what current scikit-learn returns there, with a warning;
+    older releases raised ValueError, which the reference turns into 0 -- DESIGN.md).  -> (auc, ap, wap, all_aps)"""
+    ap = np.asarray(ap, np.float64)
+    auc = np.asarray(auc, np.float64)
+    n_pos = np.asarray(n_pos, np.int64)
+    keep = n_pos > 0
+    all_aps = np.zeros(ap.shape[0], np.float64)
+    if not keep.any():
+        return 0.0, 0.0, 0.0, all_aps          # (the reference: aps = [0], mean_auc = 0)
+    aps = ap[keep]
+    weights = n_pos[keep].astype(np.float64)
+    weights /= np.sum(weights)
+    all_aps[keep] = aps
+    return float(np.mean(auc[keep])), float(np.mean(aps)), float(np.sum(np.multiply(aps, weights))), all_aps
+
+
+class DeviceMeter(object):
+    """One device buffer: hit counters, cursor, mismatch counter, score table, label table, per-class outputs, sort
+    workspace.  `update` issues kernels on the current stream and returns nothing; `read` synchronises."""
+
+    def __init__(self, kind, cols, ks=(1, 5), n_items=None, total_rows=0, device=None):
+        assert kind in ("topk", "map"), kind
+        self.kind, self.cols = kind, int(cols)
+        self.ks = tuple(int(k) for k in ks)
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.n_items = int(n_items) if n_items is not None else 0
+        self.total_rows = int(total_rows)
+        if kind == "topk":
+            if not (1 <= len(self.ks) <= 4 and all(1 <= k <= self.cols for k in self.ks)):
+                raise hip.VlfbError("DeviceMeter: ks = %r needs 1..4 values within 1..cols = %d" % (self.ks, self.cols))
+        elif self.n_items < 1:
+            raise hip.VlfbError("DeviceMeter: a 'map' meter needs n_items >= 1 (videos, or rows when nothing is merged)")
+        self._ks = hip.ks_array(self.ks)
+        # layout (bytes): hits int64[5] | cursor int64 | mismatches int32 (+pad) | ap f64[cols] | auc f64[cols] |
+        #                 n_pos int32[cols] | table f32[n][cols] | labels u8[n][cols] | sort workspace
+        n, c = self.n_items, self.cols
+        off = {"hits": 0, "cursor": 40, "mismatch": 48}
+        at = 64
+        sizes = [("ap", 8 * c), ("auc", 8 * c), ("n_pos", 4 * c)] if kind == "map" else []
+        if kind == "map":
+            self.ws_bytes = hip.query_workspace(hip.WS_CLASS_AP, (n, c)) if n > hip.CLASS_AP_LDS_MAX else 0
+            sizes += [("table", 4 * n * c), ("labels", n * c), ("ws", self.ws_bytes)]
+        for name, nbytes in sizes:
+            off[name] = at
+            at = _align(at + nbytes)
+        self.buf = torch.zeros(at, dtype=torch.uint8, device=self.device)
+        view = lambda name, nbytes, dtype: self.buf[off[name]:off[name] + nbytes].view(dtype)
+        self.hits = view("hits", 40, torch.int64)
+        self.cursor = view("cursor", 8, torch.int64)
+        self.mismatch = view("mismatch", 4, torch.int32)
+        self.head = self.buf[:64].view(torch.int64)          # hits, cursor, mismatches: what one read() copies first
+        if kind == "map":
+            self.ap, self.auc = view("ap", 8 * c, torch.float64), view("auc", 8 * c, torch.float64)
+            self.n_pos = view("n_pos", 4 * c, torch.int32)
+            self.table = view("table", 4 * n * c, torch.float32).view(n, c)
+            self.labels = view("labels", n * c, torch.uint8).view(n, c)
+            self.ws = self.buf[off["ws"]:off["ws"] + self.ws_bytes] if self.ws_bytes else None
+        self.reset()
+
+    def reset(self):
+        """asynchronous: fills on the current stream"""
+        self.head.zero_()
+        if self.kind == "map":
+            self.table.fill_(float("-inf"))
+            self.labels.fill_(255)
+
+    def update_ptr(self, scores_ptr, dtype, labels_ptr, rows):
+        """scores [rows][cols] of `dtype` and int32 labels ([rows] class indices / [rows][cols] multi-hot) by address"""
+        if self.kind == "topk":
+            hip.call("vlfb_topk_hits", scores_ptr, dtype, labels_ptr, rows, self.cols, self._ks[0], self._ks[1],
+                     hip.ptr(self.hits))
+        else:
+            hip.call("vlfb_scores_merge_max", scores_ptr, dtype, labels_ptr, rows, self.cols, hip.ptr(self.table),
+                     hip.ptr(self.labels), self.n_items, self.total_rows, hip.ptr(self.cursor), hip.ptr(self.mismatch))
+
+    def update(self, scores, labels):
+        """device tensors: scores [rows][cols] (fp32 / fp16 / bf16), labels int32"""
+        assert scores.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int32
+        assert scores.dim() == 2 and scores.shape[1] == self.cols, (tuple(scores.shape), self.cols)
+        assert labels.numel() == (scores.shape[0] if self.kind == "topk" else scores.numel())
+        self.update_ptr(scores.data_ptr(), hip.dtype_code(scores.dtype), labels.data_ptr(), scores.shape[0])
+
+    def counters(self):
+        """(hits per k ..., rows, cursor, mismatches) as Python ints; one sync"""
+        head = self.head.cpu().numpy()
+        nk = len(self.ks) if self.kind == "topk" else 0
+        return [int(v) for v in head[:nk]], int(head[nk]), int(head[5]), int(head[6] & 0xffffffff)
+
+    def filled(self, cursor):
+        n = min(cursor, self.total_rows) if self.total_rows > 0 else cursor
+        return min(n, self.n_items)
+
+    def class_scores(self, n, flags=0):
+        """per-class (ap, auc, n_pos) of the first n table rows as numpy arrays; synchronises"""
+        hip.call("vlfb_class_ap_auc", hip.ptr(self.table), hip.ptr(self.labels), n, self.cols, hip.ptr(self.ap),
+                 hip.ptr(self.auc), hip.ptr(self.n_pos), hip.ptr(self.ws), self.ws_bytes, flags)
+        return self.ap.cpu().numpy(), self.auc.cpu().numpy(), self.n_pos.cpu().numpy()
+
+    def read(self, hits=None, rows=None):
+        """the only call that synchronises.  `hits` / `rows`: counters to report instead of this meter's own (the sums
+        over data-parallel ranks, utils.metrics.MetricsCalculator)"""
+        own_hits, own_rows, cursor, mismatches = self.counters()
+        if self.kind == "topk":
+            hits = own_hits if hits is None else hits
+            rows = own_rows if rows is None else rows
+            out = {"rows": rows, "hits": dict(zip(self.ks, hits))}
+            for k, h in zip(self.ks, hits):
+                out["top%d_err" % k] = (1.0 - float(h) / rows) * 100 if rows else float("nan")
+            return out
+        n = self.filled(cursor)
+        if n < 1:
+            raise hip.VlfbError("DeviceMeter.read: no prediction has been merged yet")
+        ap, auc, n_pos = self.class_scores(n)
+        mean_auc, mean_ap, mean_wap, all_aps = summarize_ap(ap, auc, n_pos)
+        return {"mean_ap": mean_ap, "mean_wap": mean_wap, "mean_auc": mean_auc, "all_aps": all_aps, "rows": n,
+                "rows_seen": cursor, "label_mismatches": mismatches}
+
+
+def action_topk_hits(verb, noun, verb_labels, noun_labels, ks=(1, 5), prior=None):
+    """EPIC action accuracy from the stored verb / noun probabilities of two models (compute_top_k_actions,
+    tools/evaluate_actions.py:77-98): fp32 device tensors [rows][V], [rows][Nn], optional prior [V][Nn], int32 labels.
+    -> ({k: hits}, rows counted); synchronises"""
+    rows, V = verb.shape
+    Nn = noun.shape[1]
+    assert noun.shape[0] == rows and verb.dtype == noun.dtype == torch.float32 and verb.is_contiguous() and noun.is_contiguous()
+    assert verb_labels.dtype == noun_labels.dtype == torch.int32
+    assert prior is None or (tuple(prior.shape) == (V, Nn) and prior.dtype == torch.float32 and prior.is_contiguous())
+    karr, nk = hip.ks_array(ks)
+    hits = torch.zeros(5, dtype=torch.int64, device=verb.device)
+    hip.call("vlfb_action_topk_hits", hip.ptr(verb), hip.ptr(noun), hip.ptr(prior), hip.ptr(verb_labels), hip.ptr(noun_labels),
+             rows, V, Nn, karr, nk, hip.ptr(hits))
+    host = hits.cpu().numpy()
+    return {int(k): int(host[i]) for i, k in enumerate(ks)}, int(host[nk])
