@@ -382,7 +382,10 @@ int vlfb_attn_scores_bwd(const void* dy, const void* g, const void* prob, void* 
 /* ------------------------------------------------------------------------------------------
  * Small elementwise / reduction ops (rows x cols matrices of `dtype`, cols contiguous).
  * ------------------------------------------------------------------------------------------ */
-/* y = a + b (optionally relu, optionally masked by mask>0); any of y,a,b may alias.
+/* y = a + b (optionally relu, optionally masked by mask>0); any of y,a,b may alias.  b may be NULL (y = a).
+ * n == 0 is a no-op that returns VLFB_OK, here and in vlfb_relu_fwd / vlfb_relu_bwd (like the movers vlfb_cast,
+ * vlfb_zero_f32, vlfb_half_copy: an empty activation is not an error); the solver-side ops (vlfb_sgd_update*,
+ * vlfb_scale_inplace, vlfb_dropout_bwd) reject n == 0, an empty parameter bucket being a planning bug.
  * Replaces Sum (+Relu): resnet_helper.py:112-117; nonlocal_helper.py:170,201; lfb_helper.py:286 */
 int vlfb_add(const void* a, const void* b, void* y, const void* mask, int dtype, int64_t n,
              int relu, vlfb_stream_t stream);
@@ -392,7 +395,9 @@ int vlfb_relu_bwd(const void* dy, const void* y, void* dx, int dtype, int64_t n,
                   vlfb_stream_t stream);
 /* colsum[c] (+)= sum_r g[r][c] -- bias gradients of the convs that carry a bias
  * (nonlocal_helper.py:36-77, lfb_helper.py:175-200, resnet_video.py:327).  Row slabs are folded with fp32 atomics (no scratch
- * argument): not bit-reproducible.  The engine takes its bias gradients from vlfb_conv_run_wgrad_bias, which is. */
+ * argument): not bit-reproducible.  The engine takes its bias gradients from vlfb_conv_run_wgrad_bias, which is.
+ * cols and ld must be multiples of the 16-byte vector (4 fp32 / 8 16-bit elements); ld >= cols.  A rejected call launches
+ * nothing: `out` keeps its contents. */
 int vlfb_colsum(const void* g, int dtype, int64_t rows, int64_t cols, int64_t ld, float* out,
                 int accumulate, vlfb_stream_t stream);
 /* ------------------------------------------------------------------------------------------

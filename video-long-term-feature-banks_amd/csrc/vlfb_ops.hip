@@ -1666,11 +1666,13 @@ int colsum_partials(const void* g, int dtype, long long rows, long long cols, lo
 extern "C" int vlfb_colsum(const void* g, int dtype, int64_t rows, int64_t cols, int64_t ld,
                            float* out, int accumulate, vlfb_stream_t stream) {
   VLFB_REQUIRE(g && out && rows > 0 && cols > 0 && ld >= cols, "colsum: bad args");
+  VLFB_REQUIRE(dtype_ok(dtype), "colsum: bad dtype");
   hipStream_t s = (hipStream_t)stream;
-  if (!accumulate)
-    hipLaunchKernelGGL(zero_kernel, dim3(grid_for(cols, 256)), dim3(256), 0, s, out, (long long)cols);
   const int v = dtype == VLFB_F32 ? 4 : 8;
   VLFB_REQUIRE(cols % v == 0 && ld % v == 0, "colsum: cols and ld must be multiples of %d", v);
+  // (every argument check comes before the first launch: a rejected call leaves `out` as it was)
+  if (!accumulate)
+    hipLaunchKernelGGL(zero_kernel, dim3(grid_for(cols, 256)), dim3(256), 0, s, out, (long long)cols);
   const int cblocks = (int)((cols / v + 7) / 8);
   int slabs = (int)((rows + 1023) / 1024);
   const int want = (2048 + cblocks - 1) / cblocks;
