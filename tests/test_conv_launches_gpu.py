@@ -262,6 +262,82 @@ def test_model_weight_planes_are_what_weight_prep_writes():
     assert torch.equal(wi.cpu(), rows)
 
 
+# ------------------------------------------------------------------------------------------------ what the operands change
+# The plan of a descriptor is corrected by the operands of a call in three ways (resolve_for_operands, vlfb_conv_plan.hip).
+# Each case asserts the family the descriptor plans, so that a case which has moved to another kernel fails instead of
+# quietly testing nothing.
+def family_of(d):
+    return hip.conv_plan(hip.conv_desc(**d)).split()[0]
+
+
+def run_raw(d, ops, seed):
+    """run `d`, check it against the model, and return the raw bytes of O and O_lo (guard bands included)"""
+    c, _ = replay(d, ops, seed=seed)
+    return [t.cpu().view(torch.uint8) for t in (c.O, c.Olo) if t is not None]
+
+
+def assert_runs_the_tiled_kernel(d, ops, family, seed):
+    """`d` plans `family`; with these operands the launch must be, bit for bit, the one of algo = TILE128"""
+    assert family_of(d) == family, hip.conv_plan(hip.conv_desc(**d))
+    tiled = dict(d, algo=hip.ALGO_TILE128)
+    assert family_of(tiled) in ("nt", "nt_pair"), hip.conv_plan(hip.conv_desc(**tiled))
+    got, ref = run_raw(d, ops, seed), run_raw(tiled, ops, seed)
+    assert len(got) == len(ref) and all(torch.equal(a, b) for a, b in zip(got, ref)), "not the launch of algo = TILE128"
+
+
+def engine_desc(dtype, overrides, pick):
+    """first descriptor the dry-run engine of ava_r50_lfb_nl stores for which pick(dict) holds"""
+    from test_lowering import plan
+    from test_conv_launch_shrink import stored_descs
+    _, _, eng = plan("ava_r50_lfb_nl", overrides=overrides, dtype=dtype)
+    for _, d in stored_descs(eng):
+        dd = cr.desc_dict(d)
+        if pick(dd):
+            return dd
+    raise AssertionError("no such descriptor in the %s engine" % dtype)
+
+
+def epilogue_ops(d, *ops):
+    return tuple(ops) + (("bias",) if d["bias_mode"] else ())
+
+
+def test_two_term_operands_move_a_streaming_launch_to_the_tiled_kernel():
+    d = plain(cr.F16, 256, 64, 256, algo=hip.ALGO_STREAM)
+    assert_runs_the_tiled_kernel(d, ("R", "R_lo", "O_lo"), "nt_stream", seed=31)
+
+
+def test_two_term_operands_move_a_direct_conv_launch_to_the_tiled_kernel():
+    from test_conv_launch_shrink import FULL
+    d = engine_desc("fp16", FULL, lambda e: e["mode"] == cr.FPROP and (e["kt"], e["kh"], e["kw"]) == (1, 3, 3) and
+                    (e["Cs"], e["Cn"]) == (64, 64))
+    d = cr.shrink(d, lambda e: hip.conv_plan(hip.conv_desc(**e)))
+    assert_runs_the_tiled_kernel(d, epilogue_ops(d, "R", "R_lo", "O_lo"), "conv_rows64", seed=32)
+
+
+def test_a_rounded_copy_moves_a_skinny_launch_to_the_tiled_kernel():
+    d = plain(cr.F16, 33, 512, 512, out_dtype=cr.F32)
+    assert_runs_the_tiled_kernel(d, ("O_lo",), "nt_skinny", seed=33)
+
+
+@pytest.mark.parametrize("dtype,family,ops", [("fp16", "stem_fprop", ("R",)), ("mix", "stem_fprop_pair", ("R", "R_lo", "O_lo"))],
+                         ids=["fp16", "two_plane"])
+def test_a_residual_moves_the_direct_stem_to_the_tiled_kernel(dtype, family, ops):
+    # (the direct stem kernels exist for rows of 112 positions only, i.e. 224-pixel crops: the engine's descriptor at that
+    # crop, shrunk in N, T and H as far as it keeps its plan)
+    from test_conv_launch_shrink import FULL
+    d = engine_desc(dtype, FULL, lambda e: e["mode"] == cr.FPROP and e["pack_w"])
+    d = cr.shrink(d, lambda e: hip.conv_plan(hip.conv_desc(**e)))
+    assert_runs_the_tiled_kernel(d, epilogue_ops(d, *ops), family, seed=34)
+
+
+def test_thin_k_prefetch_with_and_without_a_residual():
+    d = plain(cr.F16, 300, 64, 128, relu=1)
+    words = hip.conv_plan(hip.conv_desc(**d)).split()
+    assert words[0] == "nt" and words[-1] == "pre", words
+    replay(d, ("R",), seed=35)          # the residual rows are prefetched before the k-loop
+    replay(d, (), seed=35)              # nothing to prefetch: the launch must not read R
+
+
 # ------------------------------------------------------------------------------------------------ two-plane range contract
 FP16_MAX = 65504.0
 

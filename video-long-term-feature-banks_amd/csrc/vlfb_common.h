@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include "vlfb.h"
 
 namespace vlfb {
@@ -29,6 +30,13 @@ inline int check_launch(const char* what) {
 }
 #define VLFB_REQUIRE(cond, ...) \
   do { if (!(cond)) return ::vlfb::set_error(VLFB_ERR_ARG, __VA_ARGS__); } while (0)
+
+// A/B switches: integer environment variables.  Every site keeps its value in a `static const`, so a switch is read once
+// per process; names, defaults and meanings are listed in DESIGN.md section 5.
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // ---- scalar conversions -------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }

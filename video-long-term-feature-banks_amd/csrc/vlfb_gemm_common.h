@@ -1,5 +1,5 @@
-// Shared pieces of the implicit-GEMM kernels (vlfb_gemm.hip: the 128x128 NT / TN kernels and the
-// planner; vlfb_gemm8.hip: the 256-row, 8-phase pipelined NT / TN kernels): launch parameters, gather
+// Shared pieces of the implicit-GEMM kernels (vlfb_gemm.hip: the 128x128 NT / TN kernels and the launch of a
+// plan; vlfb_conv_plan.hip: the host planner; vlfb_gemm8.hip: the 256-row, 8-phase pipelined NT / TN kernels): launch parameters, gather
 // arithmetic, the LDS swizzle, MFMA wrappers, epilogue converters and the XCD-aware workgroup remap.
 #pragma once
 #include "vlfb_common.h"
@@ -8,7 +8,7 @@
 
 namespace vlfb {
 
-// launch parameters of every implicit-GEMM kernel (filled by make_plan in vlfb_gemm.hip)
+// launch parameters of every implicit-GEMM kernel (filled by make_plan in vlfb_conv_plan.hip, pointers by conv_run_impl in vlfb_gemm.hip)
 struct GP {
   const char* A;
   const char* B;
@@ -118,6 +118,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_v;
 
 constexpr int kThreads = 256;
 constexpr int kRowBytes = 128;  // one LDS tile row = 128 bytes of K
+constexpr int kStemCT = 9;      // stem_wgrad_kernel: column tiles (16 of the K columns each) per wave
 
 
 struct RowC { int n, t, h, w; };

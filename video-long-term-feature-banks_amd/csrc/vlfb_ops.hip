@@ -483,7 +483,7 @@ __device__ __forceinline__ void stream_st8(bool nt, void* p, uint2 v) {
   else *reinterpret_cast<uint2*>(p) = v;
 }
 static bool stream_nt() {
-  static const bool on = !(getenv("VLFB_NT_EPI") && atoi(getenv("VLFB_NT_EPI")) == 0);
+  static const bool on = env_int("VLFB_NT_EPI", 1) != 0;
   return on;
 }
 __global__ void pair_split_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, long long n, bool nt) {
