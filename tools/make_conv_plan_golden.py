@@ -33,7 +33,7 @@ ALGOS = range(6)
 MAX_BYTES = 770 * 1000
 
 
-def dry_engine(preset, dtype, clips, frames, crop, split):
+def dry_engine(preset, dtype, clips, frames, crop, split, overrides=()):
     """a dry-run engine as tests/test_lowering.plan builds it, at `clips` clips of frames x crop^2"""
     from vlfb.presets import load_preset
     from core.config import config as cfg
@@ -43,7 +43,7 @@ def dry_engine(preset, dtype, clips, frames, crop, split):
     ov = ["NUM_GPUS", 1]
     for s in ("TRAIN", "TEST"):
         ov += [s + ".BATCH_SIZE", clips, s + ".VIDEO_LENGTH", frames, s + ".CROP_SIZE", crop]
-    load_preset(preset, ov)
+    load_preset(preset, ov + list(overrides))
     m = ModelBuilder(train=(split == "train"), split=split, name=split)
     m.build_model(suffix="_" + split)
     rois = 5 if clips == 2 else sum(synth.rois_per_clip_draw(clips, seed=cfg.RNG_SEED))

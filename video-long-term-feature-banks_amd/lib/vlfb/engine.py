@@ -296,6 +296,38 @@ class ConvStep(Step):
                     dt=d[0], dh=d[1], dw=d[2])
 
     def setup(self):
+        self._formats()
+        self._descriptors()
+        self._buffers()
+
+    def _weight_format(self, has_dgrad):
+        """(wcode, FPROP planes, their type, DGRAD planes, their type) of the MFMA weight operand copies: the format
+        vlfb_weight_prep writes them in, and one group's block as [planes][wblk] elements (split math: 3 bf16 term planes for
+        FPROP, 2 for DGRAD -- include/vlfb.h VLFB_SPLIT; "mix": two-term or plain fp16 DGRAD copy, per conv --
+        ConvStep._w2_geometry; a conv without a DGRAD copy goes with the engine's default)"""
+        eng = self.eng
+        bf, hf = torch.bfloat16, torch.float16
+        if not eng.mix:
+            return (hip.SPLIT, 3, bf, 2, bf) if eng.split else (eng.wcode, 1, eng.tdtype, 1, eng.tdtype)
+        dgrad = "none" if not has_dgrad else "fp32-head" if self.bwd_split else \
+            "interleaved" if self.w2i else "two-term" if self.w2 else "plain"
+        return {
+            # FPROP as split-bf16 products of the fp32 input: three bf16 term planes
+            (False, "none"): (eng.wcode, 3, bf, 1, hf),
+            (False, "plain"): (hip.MIX, 3, bf, 1, hf),
+            (False, "two-term"): (hip.MIX_W2, 3, bf, 2, hf),
+            (False, "interleaved"): (hip.MIX_W2I, 3, bf, 2, hf),
+            (False, "fp32-head"): (hip.SPLIT, 3, bf, 2, bf),
+            # a two-plane input: FPROP reads hi, lo of (w * s) * 2^10 in fp16 (a conv of the fp32 head never has one)
+            (True, "none"): (hip.MIXH_W2 if eng.MIX_W2 else hip.MIXH, 2, hf, 1, hf),
+            (True, "plain"): (hip.MIXH, 2, hf, 1, hf),
+            (True, "two-term"): (hip.MIXH_W2, 2, hf, 2, hf),
+            (True, "interleaved"): (hip.MIXH_W2I, 2, hf, 2, hf),
+        }[(self.x_pair, dgrad)]
+
+    def _formats(self):
+        """every format decision of this conv, each taken once: the flags, the keyword groups the descriptors share and the
+        dtype / math / alpha / plane fields of each descriptor (self._kw)"""
         eng = self.eng
         N, Cin, T, H, W = self.x.shape
         _, Cout, To, Ho, Wo = self.out.shape
@@ -303,29 +335,29 @@ class ConvStep(Step):
         assert not (self.stem and G > 1)
         self.Cin_k = 4 if self.stem else Cin // G     # channels as the kernel sees them (one group's)
         self.Cog = Cout // G                          # output channels of one group
-        # grouped: a launch works on a channel slice -- the tensors keep their row strides
-        ld_f = dict(lda=Cin, ldo=Cout, ldr=Cout) if G > 1 else {}
-        ld_d = dict(lda=Cout, ldo=Cin, ldr=Cin) if G > 1 else {}
-        ld_w = dict(lda=Cin, ldp=Cout) if G > 1 else {}
-        self._ld_d = ld_d
         self.pack = 8 if self.stem else 0
         code, bcode = eng.code, eng.bcode
-        geom = self._geom()
+        mf, mb = eng.math_fwd, eng.math_bwd
+        self.wblk = _prod(eng.kernel_shape(self.wname)) // G       # elements of one group's weight block
         # the gradient arriving at `out` may be stored scaled (fp16 attention logits): divide it out in the
         # epilogues of the kernels that consume it
         self.gscale = float(self.out.root.grad_scale)
+        geom = self._geom()
         if self.stem:
             # the data blob is stored with 4 zero pixels on both sides of every W row
             wpad = getattr(self.x.root, "pad_w", 0) or getattr(self.x, "pad_w", 0)
             assert wpad >= self.p[2] and wpad >= self.pack - self.k[2] + self.p[2], "stem needs a W-padded input"
             W = W + 2 * wpad
             geom["pw"] = self.p[2] - wpad
+        # the shared keyword groups: FPROP / WGRAD rows, DGRAD rows, and the leading dimensions of a grouped launch, which
+        # works on a channel slice -- the tensors keep their row strides
+        rows_f = dict(N=N, Tr=To, Hr=Ho, Wr=Wo, Ts=T, Hs=H, Ws=W, Cs=self.Cin_k, Cn=self.Cog, pack_w=self.pack)
+        rows_d = dict(N=N, Tr=T, Hr=H, Wr=W, Ts=To, Hs=Ho, Ws=Wo)
+        ld_f = dict(lda=Cin, ldo=Cout, ldr=Cout) if G > 1 else {}
+        ld_w = dict(lda=Cin, ldp=Cout) if G > 1 else {}
+        self._ld_d = dict(lda=Cout, ldo=Cin, ldr=Cin) if G > 1 else {}
         # split-bf16 math on fp32 storage (Engine dtype "split"): the weight operand copies are bf16 term planes
-        wshape = eng.kernel_shape(self.wname)
-        mf, mb = eng.math_fwd, eng.math_bwd
-        self.wblk = _prod(wshape) // G                # elements of one group's weight block
         planes = dict(b_pstride=self.wblk) if eng.split else {}
-        bplanes = planes if mb != hip.MATH_NATIVE else {}          # ("mix": split forward, native fp16 backward)
         # "mix", two-plane forward (Engine._plan_pairs): x_pair -- the input is two fp16 planes (the stem makes the clip's per
         # pass): both operands pre-split, three fp16 MFMAs per product (hip.MATH_F16X3), fp32 or two-plane output; o_pair
         # without x_pair -- an fp32 input (the attention output of a non-local block) through the split-bf16 kernel that
@@ -334,84 +366,113 @@ class ConvStep(Step):
         self.x_pair = bool(self.x.root.pair or (self.stem and eng.pair_fwd and self.o_pair))
         assert not (self.o_pair or self.x_pair) or (G == 1 and eng.mix)
         assert self.residual is None or bool(self.residual.root.pair) == self.o_pair, "residual / output formats differ: %s" % self.out.name
-        fkw = dict(N=N, Tr=To, Hr=Ho, Wr=Wo, Ts=T, Hs=H, Ws=W, Cs=self.Cin_k, Cn=self.Cog, pack_w=self.pack, relu=int(self.relu),
-                   bias_mode=hip.BIAS_COL if self.has_bias() else hip.BIAS_NONE)
-        if self.x_pair:
-            n_in = (self.x.root.numel // self.x.root.C // self.x.root.shape[-1] * W * self.Cin_k) if self.stem else self.x.root.numel
-            self.d_f = hip.conv_desc(mode=hip.FPROP, dtype=hip.F16, out_dtype=hip.F16 if self.o_pair else hip.F32, math=hip.MATH_F16X3,
-                                     a_pstride=n_in, b_pstride=_prod(eng.kernel_shape(self.wname)), alpha=1.0 / hip.MIX_W2_SCALE,
-                                     **fkw, **geom)
-        else:
-            self.d_f = hip.conv_desc(mode=hip.FPROP, dtype=code, out_dtype=hip.F16 if self.o_pair else code, math=mf,
-                                     **fkw, **planes, **geom, **ld_f)
-        self.d_d = None
-        self.d_d_full = None
-        self.w2 = False
-        self.w2i = False                # (two-term DGRAD weights interleaved per k-tile: hip.MATH_F16W2 / MIX_W2I)
-        self.bwd_split = False
-        self.dx_f32 = False
+        # the stem reads the clip: its term planes are made once per forward pass by a split pass (two fp16 planes of a
+        # two-plane forward; else 3 bf16 planes for the six-product FPROP, of which the WGRAD reads the first two next to a
+        # split pass over its output gradient).  x_pstride: elements of one plane of the input (W is the padded width here)
+        self.x_npl = 2 if (self.x_pair or mf != hip.MATH_BF16X6) else 3
+        self.x_pstride = (self.x.root.numel // self.x.root.C // self.x.root.shape[-1] * W * self.Cin_k) if self.stem else self.x.root.numel
+        self.stem_planes = self.stem and (self.x_pair or bool(eng.split and (eng.PLANES or eng.mix) and eng.STEM_PLANES))
+        has_dgrad = bool(self.x.needs_grad and not self.x.detached)
+        assert not (has_dgrad and self.stem)
+        # "mix": the gradient arriving at `out` is fp32 (Blob.grad_f32): WGRAD as split-bf16 products on the fp32 operands
         self.bwd_f32 = bool(eng.mix and self.out.root.grad_f32)
+        # ("mix": an input whose gradient slot is fp32 -- box_pooled, the attention output of a non-local block -- gets
+        # the fp32 accumulators of the fp16 DGRAD as they are, not their fp16 rounding)
+        self.dx_f32 = bool(has_dgrad and eng.mix and self.x.root.grad_f32)
+        # "mix", a conv BETWEEN fp32 gradient slots (the FBO head, Engine._plan_head_f32): its whole backward runs as
+        # on the `split` dtype -- fp32 gradient in and out, three bf16 products per product, bf16 term planes of W
+        self.bwd_split = bool(self.bwd_f32 and self.dx_f32 and G == 1)
+        assert not (self.x_pair and self.bwd_split), "a conv of the fp32 head with a two-plane input: %s" % self.out.name
+        # two-term fp16 DGRAD weights: the doubled-tap form (_w2_geometry), or -- w2i -- the same two-term product with ONE
+        # gradient tile per (Wh, Wl) pair of weight tiles (hip.MATH_F16W2 / MIX_W2I): the conv's own DGRAD geometry, weight
+        # rows [tap][Cout / 64][term][64]
+        w2 = self._w2_geometry(geom, rows_d) if (has_dgrad and eng.mix and eng.MIX_W2 and not self.bwd_split) else None
+        self.w2 = w2 is not None
+        self.w2i = bool(self.w2 and self._w2_interleaved(w2, geom, rows_d))
+        geom_d, rows_d = w2 if (self.w2 and not self.w2i) else (geom, rows_d)
+        # (Engine._plan_sparse_shortcut_dgrads) the strided 1x1x1 shortcut as an in-place accumulate over the rows it
+        # touches; d_d_full is the ordinary launch, for a pass in which this DGRAD is not an in-place second contribution
+        self._try_sparse = bool(has_dgrad and getattr(self, "sparse_dgrad", False) and not self.bwd_split and not self.dx_f32)
+        unit = tuple(self.s) == (1, 1, 1)
+        plain = unit and tuple(self.k) == (1, 1, 1) and tuple(self.p) == (0, 0, 0)
+        # Pre-split operands ("split" dtype, Engine.PLANES): a conv epilogue can write the bf16 term planes of its output
+        # next to the fp32 values (o_planes), and DGRAD / WGRAD launches that find their activation / gradient operands in
+        # that form spend no VALU on the expansion (a_planes / p_planes).  Variants are built lazily (_pl_desc).
+        self.dgrad_takes_planes = bool(eng.split and eng.PLANES and G == 1 and (plain or (unit and Cout % 32 == 0)))
+        # FPROP reads its input as planes too when the forward products are the three-term ones (two planes per operand:
+        # the LDS image of the plane DGRAD; six-term products would need three planes of both operands, 96 KiB per stage)
+        self.fprop_takes_planes = bool(eng.split and eng.PLANES and eng.FPROP_PLANES and mf == hip.MATH_BF16X3 and G == 1 and
+                                       not self.stem and (plain or self.Cin_k % 32 == 0))
+        self.wcode, self.wf_npl, self.wf_type, self.wd_npl, self.wd_type = self._weight_format(has_dgrad)
+        self.half_by_copy = False       # (True: the fp16 copy of the output comes from a copy pass, Engine._plan_half_copies)
+        self.params = [n for n in (self.wname, self.cbname) if n and eng.is_trainable(n)]
+        # a conv with a trainable bias (the non-local / FBO convs): the WGRAD launch also produces the bias gradient --
+        # db = alpha * s * column sums of the output gradient it reads anyway (vlfb_conv_run_wgrad_bias)
+        fuse_bias = bool(self.cbname and eng.is_trainable(self.cbname) and eng.FUSE_BIAS_GRAD)
+        # dtype / out_dtype / math / alpha / plane fields of the three descriptors
+        if self.x_pair:
+            fmt_f = dict(dtype=hip.F16, out_dtype=hip.F16 if self.o_pair else hip.F32, math=hip.MATH_F16X3, a_pstride=self.x_pstride,
+                         b_pstride=self.wblk, alpha=1.0 / hip.MIX_W2_SCALE)
+        else:
+            fmt_f = dict(dtype=code, out_dtype=hip.F16 if self.o_pair else code, math=mf, **planes, **ld_f)
+        alpha = 1.0 / self.gscale
+        if self.bwd_split:
+            fmt_d = dict(dtype=hip.F32, out_dtype=hip.F32, math=hip.MATH_BF16X3, alpha=alpha, **planes)
+        else:
+            # ("mix": split forward, native fp16 backward -- no term planes of W)
+            fmt_d = dict(dtype=bcode, out_dtype=hip.F32 if self.dx_f32 else bcode, math=hip.MATH_F16W2 if self.w2i else mb,
+                         alpha=alpha / hip.MIX_W2_SCALE if self.w2 else alpha, **(planes if mb != hip.MATH_NATIVE else {}))
+        fmt_w = dict(dtype=hip.F32, math=hip.MATH_BF16X3) if self.bwd_f32 else dict(dtype=bcode, math=mb)
+        self._kw = dict(
+            f=dict(fmt_f, relu=int(self.relu), bias_mode=hip.BIAS_COL if self.has_bias() else hip.BIAS_NONE, **rows_f, **geom),
+            d=dict(fmt_d, Cs=self.Cog, Cn=Cin // G, **rows_d, **geom_d, **self._ld_d) if has_dgrad else None,
+            w=dict(fmt_w, out_dtype=hip.F32, alpha=alpha, wgrad_bias=int(fuse_bias), **rows_f, **geom, **ld_w)
+            if eng.is_trainable(self.wname) else None)
+
+    def _descriptors(self):
+        """one hip.conv_desc call per descriptor, from the fields _formats chose"""
+        kw = self._kw
+        self.d_f = hip.conv_desc(mode=hip.FPROP, **kw["f"])
+        self.d_d = hip.conv_desc(mode=hip.DGRAD, **kw["d"]) if kw["d"] is not None else None
+        self.d_w = hip.conv_desc(mode=hip.WGRAD, **kw["w"]) if kw["w"] is not None else None
+        self.d_d_full = None
+        if self._try_sparse:
+            sp = hip.ConvDesc.from_buffer_copy(bytes(self.d_d))
+            sp.algo = hip.ALGO_CLASS0
+            try:
+                hip.conv_workspace_bytes(sp)
+                self.d_d_full, self.d_d = self.d_d, sp
+            except hip.VlfbError:
+                self.sparse_dgrad = False
+        self._pl = {}
+        self._ran = {}
+
+    def _buffers(self):
+        """operand copies and scratch: what this conv allocates, what it asks the engine for, and the two fp16-copy flags
+        it sets on the blobs whose gradient it reads / writes"""
+        eng = self.eng
+        Cout = self.out.shape[1]
+        wshape = tuple(eng.kernel_shape(self.wname))
+        self.w_f = torch.empty(((self.wf_npl,) if self.wf_npl > 1 else ()) + wshape, device=eng.device, dtype=self.wf_type)
+        self.w_d = torch.empty(self.wd_npl * _prod(wshape), device=eng.device, dtype=self.wd_type) if self.d_d is not None else None
+        self.x_planes = self.g_planes = None
+        if self.stem_planes:
+            self.x_planes = torch.empty(self.x_npl * self.x_pstride, device=eng.device, dtype=torch.float16 if self.x_pair else torch.bfloat16)
+            if not self.x_pair and self.d_w is not None and not eng.mix:
+                self.g_planes = torch.empty(2 * self.out.numel, device=eng.device, dtype=torch.bfloat16)
+        if self.cbname and self.sname:
+            self.eff_bias = torch.empty(Cout, device=eng.device, dtype=torch.float32)
+        if self.cbname and eng.is_trainable(self.cbname):
+            self.cb_tmp = torch.empty(Cout, device=eng.device, dtype=torch.float32)
         if self.bwd_f32:
             eng.need_scratch_act(self.out.numel)
         if eng.mix and self.x.root.grad_f32:
             eng.need_scratch_f32(self.x.numel)           # GradSlot's add path for an fp32 slot
-        if self.x.needs_grad and not self.x.detached:
-            assert not self.stem
-            dg = dict(geom)
-            alpha = 1.0 / self.gscale
-            rows = dict(N=N, Tr=T, Hr=H, Wr=W, Ts=To, Hs=Ho, Ws=Wo)
-            # "mix", a conv BETWEEN fp32 gradient slots (the FBO head, Engine._plan_head_f32): its whole backward runs as
-            # on the `split` dtype -- fp32 gradient in and out, three bf16 products per product, bf16 term planes of W
-            self.bwd_split = bool(eng.mix and self.out.root.grad_f32 and self.x.root.grad_f32 and G == 1)
-            w2 = self._w2_geometry(dg, rows) if (eng.mix and eng.MIX_W2 and not self.bwd_split) else None
-            math_d = mb
-            if w2 is not None:
-                alpha /= hip.MIX_W2_SCALE
-                self.w2 = True
-                if self._w2_interleaved(w2, dg, rows):
-                    # the same two-term product with ONE gradient tile per (Wh, Wl) pair of weight tiles (hip.MATH_F16W2): the
-                    # conv's own DGRAD geometry, weight rows [tap][Cout / 64][term][64]
-                    self.w2i = True
-                    math_d = hip.MATH_F16W2
-                else:
-                    dg, rows = w2
-            # ("mix": an input whose gradient slot is fp32 -- box_pooled, the attention output of a non-local block -- gets
-            # the fp32 accumulators of the fp16 DGRAD as they are, not their fp16 rounding)
-            self.dx_f32 = bool(eng.mix and self.x.root.grad_f32)
-            if self.dx_f32 and not self.bwd_split:
-                self.x.root.grad_half_src = True        # (this DGRAD can leave the fp16 rounding of its fp32 output: GradSlot.half_buf)
-            self.d_d = hip.conv_desc(mode=hip.DGRAD, dtype=bcode, out_dtype=hip.F32 if self.dx_f32 else bcode, Cs=self.Cog,
-                                     Cn=Cin // G, alpha=alpha, math=math_d, **rows, **bplanes, **dg, **ld_d)
-            if self.bwd_split:
-                self.d_d = hip.conv_desc(mode=hip.DGRAD, dtype=hip.F32, out_dtype=hip.F32, Cs=self.Cog, Cn=Cin // G, alpha=alpha,
-                                         math=hip.MATH_BF16X3, **rows, **planes, **dg, **ld_d)
-            # (Engine._plan_sparse_shortcut_dgrads) the strided 1x1x1 shortcut as an in-place accumulate over the rows it
-            # touches; d_d_full is the ordinary launch, for a pass in which this DGRAD is not an in-place second contribution
-            if getattr(self, "sparse_dgrad", False) and not self.bwd_split and not self.dx_f32:
-                sp = hip.ConvDesc.from_buffer_copy(bytes(self.d_d))
-                sp.algo = hip.ALGO_CLASS0
-                try:
-                    hip.conv_workspace_bytes(sp)
-                    self.d_d_full, self.d_d = self.d_d, sp
-                except hip.VlfbError:
-                    self.sparse_dgrad = False
+        if self.dx_f32 and not self.bwd_split:
+            self.x.root.grad_half_src = True        # (this DGRAD can leave the fp16 rounding of its fp32 output: GradSlot.half_buf)
         if self.bwd_f32 and self.d_d is not None and not self.bwd_split:
             self.out.root.grad_half = True      # (the fp16 DGRAD reads the fp32 output gradient rounded: GradSlot.half_buf)
-        self.d_w = None
-        if eng.is_trainable(self.wname):
-            self.d_w = hip.conv_desc(mode=hip.WGRAD, dtype=bcode, out_dtype=hip.F32, N=N, Tr=To, Hr=Ho, Wr=Wo, Ts=T,
-                                     Hs=H, Ws=W, Cs=self.Cin_k, Cn=self.Cog, pack_w=self.pack, alpha=1.0 / self.gscale,
-                                     math=mb, **geom, **ld_w)
-            # "mix": the gradient arriving at `out` is fp32 (Blob.grad_f32): WGRAD as split-bf16 products on the fp32 operands
-            self.bwd_f32 = bool(eng.mix and self.out.root.grad_f32)
-            if self.bwd_f32:
-                self.d_w = hip.conv_desc(mode=hip.WGRAD, dtype=hip.F32, out_dtype=hip.F32, N=N, Tr=To, Hr=Ho, Wr=Wo, Ts=T,
-                                         Hs=H, Ws=W, Cs=self.Cin_k, Cn=self.Cog, pack_w=self.pack, alpha=1.0 / self.gscale,
-                                         math=hip.MATH_BF16X3, **geom, **ld_w)
-            # a conv with a trainable bias (the non-local / FBO convs): the WGRAD launch also produces the bias gradient --
-            # db = alpha * s * column sums of the output gradient it reads anyway (vlfb_conv_run_wgrad_bias)
-            if self.cbname and eng.is_trainable(self.cbname) and eng.FUSE_BIAS_GRAD:
-                self.d_w.wgrad_bias = 1
+        if self.d_w is not None:
             eng.need_workspace(hip.conv_workspace_bytes(self.d_w))
             if not self.bwd_f32:
                 eng.want_half(self.x)
@@ -419,63 +480,6 @@ class ConvStep(Step):
                 # the split-bf16 WGRAD reads fp32 operands: the two planes of the input are joined into a scratch tensor
                 # right before it, on the parameter-gradient stream (whose launches run one after the other)
                 eng.need_join_scratch(self.x.numel)
-        # Pre-split operands ("split" dtype, Engine.PLANES): a conv epilogue can write the bf16 term planes of its output
-        # next to the fp32 values (o_planes), and DGRAD / WGRAD launches that find their activation / gradient operands in
-        # that form spend no VALU on the expansion (a_planes / p_planes).  Variants are built lazily (_pl_desc).
-        self._pl = {}
-        self._ran = {}
-        # the stem reads the clip: its term planes are made once per forward pass by a split pass (3 planes for the
-        # six-product FPROP, of which the WGRAD reads the first two next to a split pass over its output gradient)
-        self.x_planes = self.g_planes = None
-        if self.stem and self.x_pair:
-            self.x_planes = torch.empty(2 * self.d_f.a_pstride, device=eng.device, dtype=torch.float16)
-        elif self.stem and eng.split and (eng.PLANES or eng.mix) and eng.STEM_PLANES:
-            n_in = self.x.root.numel // self.x.root.C // self.x.root.shape[-1] * W * self.Cin_k     # W is the padded width here
-            self.x_npl = 3 if mf == hip.MATH_BF16X6 else 2
-            self.x_planes = torch.empty(self.x_npl * n_in, device=eng.device, dtype=torch.bfloat16)
-            if eng.is_trainable(self.wname) and not eng.mix:
-                self.g_planes = torch.empty(2 * self.out.numel, device=eng.device, dtype=torch.bfloat16)
-        unit = tuple(self.s) == (1, 1, 1)
-        plain = unit and tuple(self.k) == (1, 1, 1) and tuple(self.p) == (0, 0, 0)
-        self.dgrad_takes_planes = bool(eng.split and eng.PLANES and G == 1 and (plain or (unit and Cout % 32 == 0)))
-        # FPROP reads its input as planes too when the forward products are the three-term ones (two planes per operand:
-        # the LDS image of the plane DGRAD; six-term products would need three planes of both operands, 96 KiB per stage)
-        self.fprop_takes_planes = bool(eng.split and eng.PLANES and eng.FPROP_PLANES and mf == hip.MATH_BF16X3 and G == 1 and
-                                       not self.stem and (plain or self.Cin_k % 32 == 0))
-        # operand copies (split math: 3 bf16 term planes for FPROP, 2 for DGRAD -- include/vlfb.h VLFB_SPLIT)
-        if self.x_pair:
-            self.w_f = torch.empty((2,) + tuple(wshape), device=eng.device, dtype=torch.float16)     # hi, lo of (w * s) * 2^10
-        elif eng.split:
-            self.w_f = torch.empty((3,) + tuple(wshape), device=eng.device, dtype=torch.bfloat16)
-        else:
-            self.w_f = torch.empty(wshape, device=eng.device, dtype=eng.tdtype)
-        self.w_d = None
-        if self.d_d is not None:
-            if eng.mix and self.bwd_split:
-                self.w_d = torch.empty(2 * _prod(wshape), device=eng.device, dtype=torch.bfloat16)
-            elif eng.mix:
-                self.w_d = torch.empty((2 if self.w2 else 1) * _prod(wshape), device=eng.device, dtype=torch.float16)
-            else:
-                self.w_d = (torch.empty(2 * _prod(wshape), device=eng.device, dtype=torch.bfloat16) if eng.split else
-                            torch.empty(_prod(wshape), device=eng.device, dtype=eng.tdtype))
-        # one group's weight-operand block: [planes][wblk] elements, group g at g * planes * wblk (vlfb_weight_prep* is run
-        # per group, so the term planes of a group lie next to each other)
-        self.wf_npl = 2 if self.x_pair else 3 if eng.split else 1
-        self.wd_npl = (2 if (self.w2 or self.bwd_split) else 1) if eng.mix else (2 if eng.split else 1)
-        # the format vlfb_weight_prep writes this conv's operand copies in ("mix": two-term or plain fp16 DGRAD copy, per conv --
-        # ConvStep._w2_geometry; a conv without a DGRAD copy goes with the engine's default)
-        self.wcode = eng.wcode if not eng.mix else (hip.SPLIT if self.bwd_split else
-                                                    hip.MIX if (self.w_d is not None and not self.w2) else
-                                                    hip.MIX_W2I if self.w2i else eng.wcode)
-        if self.x_pair:
-            assert not self.bwd_split, "a conv of the fp32 head with a two-plane input: %s" % self.out.name
-            self.wcode = {hip.MIX: hip.MIXH, hip.MIX_W2: hip.MIXH_W2, hip.MIX_W2I: hip.MIXH_W2I}[self.wcode]
-        self.half_by_copy = False       # (True: the fp16 copy of the output comes from a copy pass, Engine._plan_half_copies)
-        if self.cbname and self.sname:
-            self.eff_bias = torch.empty(Cout, device=eng.device, dtype=torch.float32)
-        self.params = [n for n in (self.wname, self.cbname) if n and eng.is_trainable(n)]
-        if self.cbname and eng.is_trainable(self.cbname):
-            self.cb_tmp = torch.empty(Cout, device=eng.device, dtype=torch.float32)
 
     def _w2_geometry(self, dg, rows):
         """"mix", two-term fp16 DGRAD weights (hip.MIX_W2): the same convolution with a doubled OUTERMOST tap dimension of
@@ -579,62 +583,68 @@ class ConvStep(Step):
         self._ran[id(base)] = d           # the variant of `base` that was launched last (Engine.plan_table(launched=True))
         return d
 
+    def _run(self, d, A, B, P, O, **ops):
+        """the launch of `d`.  A grouped conv runs as G launches on channel SLICES: block g of the outputs reads block g of the
+        inputs and weight block g -- input-side operands advance by Cin_k, output-side ones by Cog (DGRAD: the gradient
+        operand is the output side, what it writes the input side), a WGRAD's output by one group's weight block"""
+        if self.group == 1:
+            return hip.conv_run(d, A, B, P, O, **ops)
+        dgrad = d.mode == hip.DGRAD
+        a, o = (self.Cog, self.Cin_k) if dgrad else (self.Cin_k, self.Cog)
+        ws = ops.pop("workspace", None)
+        for g in range(self.group):
+            W = None if B is None else self.wd_ptr(g) if dgrad else self.wf_ptr(g)
+            hip.conv_run(d, _at(A, g * a), W, _at(P, g * self.Cog), _at(O, g * (self.wblk if d.mode == hip.WGRAD else o)),
+                         workspace=ws, **{k: _at(v, g * o) for k, v in ops.items()})
+
     def fwd(self):
         R = self.residual.storage() if self.residual is not None else None
-        op = self.out.root.planes
+        A, d, half = self.x.storage(), self.d_f, self.out.root.half
+        ops = dict(bias=self.bias_tensor(), R=R)
         if self.x_pair or self.o_pair:
-            A = self.x.storage()
             if self.x_planes is not None:         # the stem: the clip's two fp16 planes, made per pass
-                hip.call("vlfb_pair_split", self.x.ptr(), hip.ptr(self.x_planes), self.x_planes.numel() // 2)
+                hip.call("vlfb_pair_split", self.x.ptr(), hip.ptr(self.x_planes), self.x_pstride)
                 A = self.x_planes
             if self.o_pair:
-                hip.conv_run(self.d_f, A, self.w_f, None, self.out.storage(), bias=self.bias_tensor(), R=R,
-                             R_lo=self.residual.lo() if R is not None else None, O_lo=self.out.lo())
+                ops.update(R_lo=self.residual.lo() if R is not None else None, O_lo=self.out.lo())
             else:
                 # fp32 output (theta / phi / g of a non-local block); O_lo = the fp16 copy the backward reads, if it wants one
                 assert R is None
-                hip.conv_run(self.d_f, A, self.w_f, None, self.out.storage(), bias=self.bias_tensor(), O_lo=self.out.root.half)
-            return
-        if self.x_planes is not None:
-            n = self.x_planes.numel() // self.x_npl
-            hip.call("vlfb_split_planes", self.x.ptr(), hip.ptr(self.x_planes), self.x_npl, 1, n // 8, 8, 0)
-            kw = dict(a_planes=self.x_npl, a_pstride=n)
-            oh = self.out.root.half
-            if oh is not None:
+                ops.update(O_lo=half)
+        elif self.x_planes is not None:           # the stem on split math: the clip's bf16 term planes, made per pass
+            hip.call("vlfb_split_planes", self.x.ptr(), hip.ptr(self.x_planes), self.x_npl, 1, self.x_pstride // 8, 8, 0)
+            A = self.x_planes
+            kw = dict(a_planes=self.x_npl, a_pstride=self.x_pstride)
+            if half is not None:
                 kw.update(o_planes=1)
-            hip.conv_run(self._pl_desc(self.d_f, **kw), self.x_planes, self.w_f, None, self.out.storage(),
-                         bias=self.bias_tensor(), R=R, O_planes=oh)
-            return
-        xp = self.x.root.planes if self.fprop_takes_planes else None
-        kw = {}
-        if xp is not None:
-            kw.update(a_planes=2, a_pstride=xp.numel() // 2)
-        if op is not None:
-            kw.update(o_planes=2, o_pstride=op.numel() // 2)
-        elif self.out.root.half is not None:       # "mix": the fp16 copy the backward reads, written by this epilogue
-            op = self.out.root.half
-            kw.update(o_planes=1)
-        d = self._pl_desc(self.d_f, **kw) if kw else self.d_f
-        if self.group == 1:
-            hip.conv_run(d, self.x.storage() if xp is None else xp, self.w_f, None,
-                         self.out.storage(), bias=self.bias_tensor(), R=R, O_planes=op)
-            return
-        xs, os_, bt = self.x.storage(), self.out.storage(), self.bias_tensor()
-        for g in range(self.group):                # channel slices: block g of the outputs reads block g of the inputs
-            hip.conv_run(d, _at(xs, g * self.Cin_k), self.wf_ptr(g), None, _at(os_, g * self.Cog), bias=_at(bt, g * self.Cog),
-                         R=_at(R, g * self.Cog), O_planes=_at(op, g * self.Cog))
+            ops.update(O_planes=half)
+            d = self._pl_desc(d, **kw)
+        else:
+            xp = self.x.root.planes if self.fprop_takes_planes else None
+            op = self.out.root.planes
+            kw = {}
+            if xp is not None:
+                A = xp
+                kw.update(a_planes=2, a_pstride=xp.numel() // 2)
+            if op is not None:
+                kw.update(o_planes=2, o_pstride=op.numel() // 2)
+            elif half is not None:                 # "mix": the fp16 copy the backward reads, written by this epilogue
+                op = half
+                kw.update(o_planes=1)
+            ops.update(O_planes=op)
+            if kw:
+                d = self._pl_desc(d, **kw)
+        self._run(d, A, self.w_f, None, self.out.storage(), **ops)
 
     def bwd(self):
         eng = self.eng
         g = g_w = self.out_grad()
-        if self.bwd_f32:
+        if self.bwd_f32 and self.d_d is not None and not self.bwd_split:
             # fp32 gradient ("mix", non-local theta / phi / g): WGRAD and the bias sum read it as it is, DGRAD its fp16 copy
-            g_w = g
-            if self.d_d is not None and not self.bwd_split:
-                g = self.out.root.slot.value_half()       # (left by the launch that produced the gradient: GradSlot.half_buf)
-                if g is None:
-                    g = eng.scratch_act(self.out.numel)
-                    hip.call("vlfb_cast", hip.ptr(g_w), hip.F32, hip.ptr(g), eng.bcode, self.out.numel)
+            g = self.out.root.slot.value_half()       # (left by the launch that produced the gradient: GradSlot.half_buf)
+            if g is None:
+                g = eng.scratch_act(self.out.numel)
+                hip.call("vlfb_cast", hip.ptr(g_w), hip.F32, hip.ptr(g), eng.bcode, self.out.numel)
         gp = self.out.root.slot.value_planes()         # term planes of the finished output gradient, or None
         if self.residual is not None and self.residual.needs_grad and not self.residual.detached:
             self.residual.root.slot.contribute_alias(g, self.out.root.slot.value_lo())
@@ -645,7 +655,7 @@ class ConvStep(Step):
         if self.d_d is not None and self.bwd_split:
             # (the FBO head) fp32 gradient operand, fp32 slot: the split-bf16 DGRAD with the slot's earlier contribution and
             # the fp32 values as the ReLU mask in its epilogue
-            self.x.root.slot.contribute(lambda out, add, mask: hip.conv_run(self.d_d, g_w, self.w_d, None, out, R=add, mask=mask))
+            self.x.root.slot.contribute(lambda out, add, mask: self._run(self.d_d, g_w, self.w_d, None, out, R=add, mask=mask))
         elif self.d_d is not None and eng.mix and self.x.root.grad_f32:
             # (Engine._plan_head_f32, AttentionStep) the input's gradient slot is fp32: the fp16 DGRAD writes its fp32
             # accumulators there (out_dtype F32; GradSlot adds an earlier contribution in fp32)
@@ -654,7 +664,7 @@ class ConvStep(Step):
 
             def dgrad_f32(out, add, mask):
                 hb = xs.half_dest(out, add, mask)
-                hip.conv_run(self.d_d, g, self.w_d, None, out, O_lo=hb)
+                self._run(self.d_d, g, self.w_d, None, out, O_lo=hb)
                 xs.half_valid = hb is not None
             xs.contribute(dgrad_f32, supports_add=False, supports_mask=False)
         elif self.d_d is not None:
@@ -675,15 +685,8 @@ class ConvStep(Step):
                     (xs.out_lo is None or (xs.add_lo is not None and xs.add_lo.data_ptr() == xs.out_lo.data_ptr()))
                 if self.d_d_full is not None and not inplace:
                     base = self.d_d_full          # (not an in-place second contribution: the launch that writes every row)
-                d = self._pl_desc(base, **kw) if kw else base
-                if self.group == 1:
-                    hip.conv_run(d, gp if a_pl else g, self.w_d, None, out, R=add, mask=mask, O_planes=planes,
-                                 R_lo=xs.add_lo, O_lo=xs.out_lo)
-                    return
-                for gi in range(self.group):
-                    c = gi * self.Cin_k
-                    hip.conv_run(d, _at(g, gi * self.Cog), self.wd_ptr(gi), None, _at(out, c), R=_at(add, c), mask=_at(mask, c),
-                                 O_planes=_at(planes, c), R_lo=_at(xs.add_lo, c), O_lo=_at(xs.out_lo, c))
+                self._run(self._pl_desc(base, **kw) if kw else base, gp if a_pl else g, self.w_d, None, out, R=add, mask=mask,
+                          O_planes=planes, R_lo=xs.add_lo, O_lo=xs.out_lo)
             self.x.root.slot.contribute(dgrad, writes_planes=True)
 
     def _x_f32(self):
@@ -699,30 +702,21 @@ class ConvStep(Step):
         if self.d_w is not None:
             s = eng.param_tensor(self.sname) if self.sname else None
             xp = self.x.root.planes
+            d, gb = self.d_w, None
             if self.g_planes is not None:          # stem: both operands through a split pass (the clip's planes exist)
-                n = self.x_planes.numel() // self.x_npl
                 hip.call("vlfb_split_planes", hip.ptr(g), hip.ptr(self.g_planes), 2, 1, self.out.numel // 8, 8, 0)
-                d = self._pl_desc(self.d_w, a_planes=self.x_npl, a_pstride=n, p_planes=2, p_pstride=self.out.numel)
-                hip.conv_run(d, self.x_planes, None, self.g_planes, eng.grad_tensor(self.wname), rowscale=s, workspace=eng.workspace)
+                d = self._pl_desc(d, a_planes=self.x_npl, a_pstride=self.x_pstride, p_planes=2, p_pstride=self.out.numel)
+                A, P = self.x_planes, self.g_planes
             elif gp is not None and xp is not None and not self.stem and self.group == 1:
                 # both operands pre-split: DMA + transposed LDS reads, no VALU in the k-loop
-                d = self._pl_desc(self.d_w, a_planes=2, a_pstride=xp.numel() // 2, p_planes=2, p_pstride=gp.numel() // 2, wgrad_bias=0)
-                hip.conv_run(d, xp, None, gp, eng.grad_tensor(self.wname), rowscale=s, workspace=eng.workspace)
-            elif self.group > 1:
-                xsrc, gw = (self._x_f32() if self.bwd_f32 else self.x.bstorage()), eng.grad_tensor(self.wname)
-                gb = eng.grad_tensor(self.cbname) if self.d_w.wgrad_bias else None
-                for gi in range(self.group):
-                    hip.conv_run(self.d_w, _at(xsrc, gi * self.Cin_k), None, _at(g, gi * self.Cog), _at(gw, gi * self.wblk),
-                                 rowscale=_at(s, gi * self.Cog), workspace=eng.workspace, dbias=_at(gb, gi * self.Cog))
-                if gb is not None:
-                    return
-            elif self.d_w.wgrad_bias:
-                hip.conv_run(self.d_w, self._x_f32() if self.bwd_f32 else self.x.bstorage(), None, g,
-                             eng.grad_tensor(self.wname), rowscale=s, workspace=eng.workspace, dbias=eng.grad_tensor(self.cbname))
-                return
+                d = self._pl_desc(d, a_planes=2, a_pstride=xp.numel() // 2, p_planes=2, p_pstride=gp.numel() // 2, wgrad_bias=0)
+                A, P = xp, gp
             else:
-                hip.conv_run(self.d_w, self._x_f32() if self.bwd_f32 else self.x.bstorage(), None, g,
-                             eng.grad_tensor(self.wname), rowscale=s, workspace=eng.workspace)
+                A, P = (self._x_f32() if self.bwd_f32 else self.x.bstorage()), g
+                gb = eng.grad_tensor(self.cbname) if d.wgrad_bias else None
+            self._run(d, A, None, P, eng.grad_tensor(self.wname), rowscale=s, workspace=eng.workspace, dbias=gb)
+            if gb is not None:                      # (the launch produced the bias gradient as well)
+                return
             if self.stem:   # keep the zero padding of the packed stem weight exactly zero
                 gw = eng.grad_tensor(self.wname)
                 hip.call("vlfb_add", hip.ptr(gw), None, hip.ptr(gw), hip.ptr(eng.stem_mask), hip.F32,
