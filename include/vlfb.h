@@ -214,9 +214,10 @@ int vlfb_conv_plan_describe(const vlfb_conv_desc* d, char* buf, int64_t buf_byte
  *   VLFB_WS_ATTN_SCORES    arg = const int64_t[3] {b, l1, l2}     fp32 score matrix between the scores GEMM and
  *                                                                vlfb_softmax_fwd / _bwd when the fused kernels are not used
  *   VLFB_WS_BN             arg = const int64_t[3] {dtype, rows, C} `workspace` of vlfb_bn_fwd / _bwd (= vlfb_bn_workspace_bytes)
- *   VLFB_WS_CLASS_AP       arg = const int64_t[2] {n, cols}       `workspace` of vlfb_class_ap_auc (its global sort path) */
+ *   VLFB_WS_CLASS_AP       arg = const int64_t[2] {n, cols}       `workspace` of vlfb_class_ap_auc (its global sort path)
+ *   VLFB_WS_CLASS_AP_VOC   arg = const int64_t[2] {n, cols}       `workspace` of vlfb_class_ap_voc (its global sort path) */
 enum { VLFB_WS_CONV = 0, VLFB_WS_MAXPOOL_ARGMAX = 1, VLFB_WS_FBO_ATTN_BWD = 2, VLFB_WS_ATTN_SCORES = 3, VLFB_WS_BN = 4,
-       VLFB_WS_CLASS_AP = 5 };
+       VLFB_WS_CLASS_AP = 5, VLFB_WS_CLASS_AP_VOC = 6 };
 int64_t vlfb_query_workspace(int op, const void* arg);
 /* A: activation / gradient operand; B: weight operand (FPROP/DGRAD) or unused (WGRAD);
  * P: WGRAD output-gradient operand; O: output; bias/rowscale: fp32 vectors or NULL;
@@ -645,6 +646,46 @@ int vlfb_scores_merge_max(const void* scores, int dtype, const int32_t* labels, 
 enum { VLFB_CLASS_AP_FORCE_GLOBAL = 1 };
 int vlfb_class_ap_auc(const float* table, const uint8_t* table_labels, int64_t n, int64_t cols, double* ap, double* auc,
                       int32_t* n_pos, void* workspace, int64_t workspace_bytes, int flags, vlfb_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * AVA frame-mAP: the PASCAL-VOC detection protocol at IoU 0.5, as the AVA evaluator applies it.  The
+ * reference ships no evaluator (utils/ava_eval_helper.py imports utils.ava_evaluation.*, which is absent), so what is
+ * pinned here is the protocol itself; tests/ava_eval_ref.py restates it in fp64.
+ * ------------------------------------------------------------------------------------------ */
+/* True / false positive of every (detection row, class).  scores fp32 [n_rows][cols] is the meter's score table (class id
+ * = column + 1); det_box fp64 [n_rows][4] = (x1, y1, x2, y2) by table row.  Images are two CSRs over n_img images:
+ * img_det_ptr / det_rows (the table rows of each image's detections; a row is named at most once) and img_gt_ptr /
+ * gt_box fp64 [.][4] / gt_class int32 [.] (one row per (box, label), in file order within an image).  Both pointer arrays
+ * are given twice: in device memory for the kernel, and as HOST copies (host_img_*_ptr) the entry point checks before it
+ * launches -- an image with more than VLFB_AVA_MAX_DET detections or VLFB_AVA_MAX_GT ground-truth rows is refused with a
+ * message that names it; nothing is ever truncated.  The device and the host copy of a pointer array MUST be identical
+ * (vlfb.metrics.ava_frame_ap uploads the array it passes): if they differ the outputs are undefined -- the kernel only
+ * keeps its own reads and writes inside the arrays it was given.  class_mask uint8 [cols]: 1 = whitelisted.
+ * Outputs: tp uint8 [n_rows][cols], first filled with 255, then 0 / 1 for every (row of det_rows, whitelisted class);
+ * n_gt int32 [cols], the ground-truth rows of every whitelisted class (0 for the others).
+ * One image, one class c: G = its ground-truth rows of class c in stored order; D = all its detection rows by
+ * (scores[row][c] descending, row ascending).  IoU in fp64: iw = min(x2a, x2b) - max(x1a, x1b), ih likewise,
+ * inter = max(iw, 0) * max(ih, 0), iou = inter / (area_a + area_b - inter), area = (x2 - x1) * (y2 - y1).  G empty: every
+ * detection is a false positive.  Otherwise, in that order, g* = the FIRST index of the maximum IoU over G; the detection is
+ * a true positive iff iou(d, g*) >= 0.5 and g* is not yet taken, and g* then becomes taken.  A detection whose best box is
+ * taken does NOT fall back to its second-best box.  Scores must not be NaN.  No atomics: every output byte has one writer. */
+#define VLFB_AVA_MAX_DET 128
+#define VLFB_AVA_MAX_GT 128
+int vlfb_ava_match_tp(const float* scores, const double* det_box, int64_t n_rows, int64_t cols, const int32_t* img_det_ptr,
+                      const int32_t* det_rows, const int32_t* img_gt_ptr, const double* gt_box, const int32_t* gt_class,
+                      int64_t n_img, const int32_t* host_img_det_ptr, const int32_t* host_img_gt_ptr, const uint8_t* class_mask,
+                      uint8_t* tp, int32_t* n_gt, vlfb_stream_t stream);
+/* PASCAL AP per class c from scores [n][cols], tp [n][cols] and n_gt [cols] (compute_average_precision of the public
+ * evaluator: sentinels 0 and 1, precision made non-increasing from the right, summed where recall changes): the rows
+ * whose tp is 0 or 1, sorted by (score descending, row ascending); ctp_i = true positives in positions 0..i,
+ * p_i = ctp_i / (i + 1);  AP = (1 / n_gt) * sum over true-positive positions i of max_{j >= i} p_j.  The maximum is taken
+ * over exact integer fractions; every term is one fp64 division ctp_j / ((j + 1) * n_gt), summed in a fixed order.
+ * n_gt[c] <= 0 (a class without ground truth, a masked class): NaN; n_gt[c] > 0 and no detection: 0.
+ * n <= 4096: the column is sorted in LDS; above that, or with VLFB_CLASS_AP_FORCE_GLOBAL, the same network runs over
+ * `workspace` (vlfb_query_workspace(VLFB_WS_CLASS_AP_VOC, {n, cols}) bytes), up to n = VLFB_CLASS_AP_MAX_N.  Both paths
+ * give bit-identical results. */
+int vlfb_class_ap_voc(const float* scores, const uint8_t* tp, const int32_t* n_gt, int64_t n, int64_t cols, double* ap,
+                      void* workspace, int64_t workspace_bytes, int flags, vlfb_stream_t stream);
 
 #ifdef __cplusplus
 }

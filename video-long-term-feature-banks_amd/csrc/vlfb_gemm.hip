@@ -892,6 +892,7 @@ int launch_plan(const vlfb_conv_desc* d, const Plan& pl, hipStream_t s) {
 using namespace vlfb;
 
 int64_t vlfb_class_ap_workspace_bytes_impl(int64_t n, int64_t cols);   // vlfb_metrics.hip
+int64_t vlfb_class_ap_voc_workspace_bytes_impl(int64_t n, int64_t cols);
 extern "C" int64_t vlfb_query_workspace(int op, const void* arg) {
   if (!arg) { set_error(VLFB_ERR_ARG, "query_workspace: arg is required"); return -1; }
   switch (op) {
@@ -922,6 +923,12 @@ extern "C" int64_t vlfb_query_workspace(int op, const void* arg) {
       const int64_t* v = static_cast<const int64_t*>(arg);
       const int64_t n = vlfb_class_ap_workspace_bytes_impl(v[0], v[1]);
       if (n < 0) set_error(VLFB_ERR_ARG, "query_workspace: class_ap needs 1 <= n <= %d and cols >= 1", VLFB_CLASS_AP_MAX_N);
+      return n;
+    }
+    case VLFB_WS_CLASS_AP_VOC: {
+      const int64_t* v = static_cast<const int64_t*>(arg);
+      const int64_t n = vlfb_class_ap_voc_workspace_bytes_impl(v[0], v[1]);
+      if (n < 0) set_error(VLFB_ERR_ARG, "query_workspace: class_ap_voc needs 1 <= n <= %d and cols >= 1", VLFB_CLASS_AP_MAX_N);
       return n;
     }
     default: set_error(VLFB_ERR_ARG, "query_workspace: unknown op %d", op); return -1;

@@ -350,3 +350,275 @@ extern "C" int vlfb_class_ap_auc(const float* table, const uint8_t* table_labels
   class_ap_auc_global_kernel<<<(unsigned)cols, AP_THREADS, 0, s>>>(table, table_labels, (int)n, (int)cols, npad, wk, wl, ap, auc, n_pos);
   return check_launch("class_ap_auc");
 }
+
+// ---- AVA frame-mAP (include/vlfb.h, "AVA frame-mAP"): PASCAL-VOC matching at IoU 0.5 and the envelope AP -----------------
+namespace vlfb {
+
+constexpr int AVA_THREADS = 128;               // a lane owns a class (classes beyond 128 are walked in further rounds)
+constexpr int AVA_DCHUNK = 32;                 // detections whose IoU row is staged at a time: 32 x 128 fp64 = 32 KiB
+constexpr int AVA_NONE = 255;                  // "no ground-truth box at IoU >= 0.5" in the best-box table
+
+__global__ void ava_fill_tp_kernel(uint8_t* __restrict__ tp, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) tp[i] = 255;
+}
+
+// ground-truth rows per whitelisted class: a workgroup per class, integer partial counts, one writer
+__global__ __launch_bounds__(256) void ava_count_gt_kernel(const int32_t* __restrict__ gt_class, int n_gt_rows,
+                                                           const uint8_t* __restrict__ class_mask, int32_t* __restrict__ n_gt) {
+  __shared__ int part[4];
+  const int c = blockIdx.x;
+  int cnt = 0;
+  if (class_mask[c])
+    for (int i = threadIdx.x; i < n_gt_rows; i += 256) cnt += gt_class[i] == c + 1 ? 1 : 0;
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) n_gt[c] = part[0] + part[1] + part[2] + part[3];
+}
+
+__device__ __forceinline__ double box_area(const double* b) { return (b[2] - b[0]) * (b[3] - b[1]); }
+
+// One workgroup per image.  Phase 1 (per chunk of detections): the IoU rows in LDS, then the lane of class c finds, for
+// every detection of the chunk, the FIRST index of the maximum IoU over the image's class-c boxes and keeps it when that
+// IoU reaches 0.5.  Phase 2: the lane walks the image's detections by (score of its class descending, table row ascending)
+// with the taken boxes as a bitmask in registers.  A best box that is taken makes a false positive: no second choice.
+__global__ __launch_bounds__(AVA_THREADS) void ava_match_kernel(
+    const float* __restrict__ scores, const double* __restrict__ det_box, int n_rows, int cols,
+    const int32_t* __restrict__ img_det_ptr, const int32_t* __restrict__ det_rows, int n_det,
+    const int32_t* __restrict__ img_gt_ptr, const double* __restrict__ gt_box, const int32_t* __restrict__ gt_class, int n_gt_rows,
+    const uint8_t* __restrict__ class_mask, uint8_t* __restrict__ tp) {
+  __shared__ double s_db[VLFB_AVA_MAX_DET][4];
+  __shared__ double s_gb[VLFB_AVA_MAX_GT][4];
+  __shared__ double s_iou[AVA_DCHUNK][VLFB_AVA_MAX_GT];
+  __shared__ int s_row[VLFB_AVA_MAX_DET];
+  __shared__ int s_gc[VLFB_AVA_MAX_GT];
+  __shared__ uint8_t s_best[VLFB_AVA_MAX_DET][AVA_THREADS];
+  const int img = blockIdx.x, t = threadIdx.x;
+  // The entry point has checked the HOST copy of both CSRs, which the device copy must equal (include/vlfb.h): with equal
+  // copies no clamp below ever acts.  They only keep the reads and writes of a call that breaks that rule inside the arrays;
+  // its results are undefined, not a truncated evaluation.
+  const int d_lo = min(max(img_det_ptr[img], 0), n_det), g_lo = min(max(img_gt_ptr[img], 0), n_gt_rows);
+  const int nd = min(max(min(img_det_ptr[img + 1], n_det) - d_lo, 0), VLFB_AVA_MAX_DET);
+  const int ng = min(max(min(img_gt_ptr[img + 1], n_gt_rows) - g_lo, 0), VLFB_AVA_MAX_GT);
+  if (nd == 0) return;                                          // (block-uniform) ground truth only: counted by ava_count_gt_kernel
+  for (int i = t; i < nd; i += AVA_THREADS) {
+    const int row = det_rows[d_lo + i];
+    const bool ok = row >= 0 && row < n_rows;
+    s_row[i] = ok ? row : -1;
+    for (int k = 0; k < 4; ++k) s_db[i][k] = ok ? det_box[(size_t)row * 4 + k] : 0.0;
+  }
+  for (int i = t; i < ng; i += AVA_THREADS) {
+    s_gc[i] = gt_class[g_lo + i];
+    for (int k = 0; k < 4; ++k) s_gb[i][k] = gt_box[(size_t)(g_lo + i) * 4 + k];
+  }
+  for (int cb = 0; cb < cols; cb += AVA_THREADS) {              // one round when cols <= 128: the IoU rows are formed once per image
+    const int c = cb + t;
+    const bool active = c < cols && class_mask[c] != 0;
+    for (int d0 = 0; d0 < nd; d0 += AVA_DCHUNK) {
+      const int dn = min(AVA_DCHUNK, nd - d0);
+      __syncthreads();                                          // boxes staged / the previous chunk's rows read
+      for (int e = t; e < dn * ng; e += AVA_THREADS) {
+        const int di = e / ng, g = e - di * ng;
+        const double* a = s_db[d0 + di];
+        const double* b = s_gb[g];
+        const double iw = fmin(a[2], b[2]) - fmax(a[0], b[0]);
+        const double ih = fmin(a[3], b[3]) - fmax(a[1], b[1]);
+        const double inter = fmax(iw, 0.0) * fmax(ih, 0.0);
+        s_iou[di][g] = inter / (box_area(a) + box_area(b) - inter);
+      }
+      __syncthreads();
+      if (active)
+        for (int di = 0; di < dn; ++di) {
+          int best = -1;
+          double bv = 0.0;
+          for (int g = 0; g < ng; ++g)
+            if (s_gc[g] == c + 1) {
+              const double v = s_iou[di][g];
+              if (best < 0 || v > bv) { best = g; bv = v; }     // strict: the first index of the maximum
+            }
+          s_best[d0 + di][t] = (best >= 0 && bv >= 0.5) ? (uint8_t)best : (uint8_t)AVA_NONE;
+        }
+    }
+    if (active) {
+      unsigned long long done0 = 0, done1 = 0, taken0 = 0, taken1 = 0;
+      for (int i = 0; i < nd; ++i)
+        if (s_row[i] < 0) { if (i < 64) done0 |= 1ull << i; else done1 |= 1ull << (i - 64); }
+      for (int step = 0; step < nd; ++step) {
+        int pick = -1, prow = 0;
+        float ps = 0.f;
+        for (int i = 0; i < nd; ++i) {
+          if ((i < 64 ? done0 >> i : done1 >> (i - 64)) & 1ull) continue;
+          const int row = s_row[i];
+          const float s = scores[(size_t)row * cols + c];
+          if (pick < 0 || s > ps || (s == ps && row < prow)) { pick = i; ps = s; prow = row; }
+        }
+        if (pick < 0) break;
+        if (pick < 64) done0 |= 1ull << pick; else done1 |= 1ull << (pick - 64);
+        const int b = s_best[pick][t];
+        uint8_t hit = 0;
+        if (b != AVA_NONE) {
+          const bool was = (b < 64 ? taken0 >> b : taken1 >> (b - 64)) & 1ull;
+          if (!was) {
+            hit = 1;
+            if (b < 64) taken0 |= 1ull << b; else taken1 |= 1ull << (b - 64);
+          }
+        }
+        tp[(size_t)prow * cols + c] = hit;
+      }
+    }
+  }
+}
+
+// PASCAL AP of one class.  key = order_key(score) << 32 | (0x7fffffff - row) << 1 | tp, 0 for rows without a verdict and
+// for the padding: descending order of the key is (score descending, row ascending) with the dropped rows behind everything.
+constexpr int VOC_LDS_MAX = 4096;              // 8 B per key: 32 KiB beside the scan and sum buffers
+
+// a / b > c / d for non-negative numerators and positive denominators below 2^31: exact
+__device__ __forceinline__ bool frac_gt(int a, int b, int c, int d) { return (long long)a * d > (long long)c * b; }
+
+__device__ __forceinline__ void class_ap_voc_body(const float* __restrict__ scores, const uint8_t* __restrict__ tpv,
+                                                  const int32_t* __restrict__ n_gt, int n, int cols, int npad,
+                                                  unsigned long long* keys, int* ibuf, double* dbuf, double* __restrict__ ap) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  for (int i = t; i < npad; i += AP_THREADS) {
+    unsigned long long k = 0;
+    if (i < n) {
+      const uint8_t v = tpv[(size_t)i * cols + c];
+      if (v <= 1)
+        k = ((unsigned long long)order_key(scores[(size_t)i * cols + c]) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)i) << 1) | v;
+    }
+    keys[i] = k;
+  }
+  __syncthreads();
+  for (int k = 2; k <= npad; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = t; p < (npad >> 1); p += AP_THREADS) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+        const int l = i | j;
+        const bool desc = (i & k) == 0;
+        const unsigned long long a = keys[i], b = keys[l];
+        if (desc ? a < b : a > b) { keys[i] = b; keys[l] = a; }
+      }
+      __syncthreads();
+    }
+  // thread t owns the chunk [lo, hi) of the sorted column; rows with a verdict come first
+  const int L = (npad + AP_THREADS - 1) / AP_THREADS;
+  const int lo = min(t * L, npad), hi = min(lo + L, npad);
+  int cnt = 0, last = lo - 1;                                    // true positives of the chunk; its last row with a verdict
+  for (int i = lo; i < hi; ++i)
+    if (keys[i] != 0) { cnt += (int)(keys[i] & 1ull); last = i; }
+  const int before = block_exclusive<false>(cnt, 0, ibuf);       // true positives in [0, lo)
+  // the chunk's largest precision ctp_i / (i + 1), as an exact fraction (0 / 1 when the chunk holds no row)
+  int bn = 0, bd = 1, ctp = before;
+  for (int i = lo; i <= last; ++i) {
+    ctp += (int)(keys[i] & 1ull);
+    if (frac_gt(ctp, i + 1, bn, bd)) { bn = ctp; bd = i + 1; }
+  }
+  ibuf[t] = bn;
+  ibuf[AP_THREADS + t] = bd;
+  __syncthreads();
+  int sn = 0, sd = 1;                                            // suffix maximum over the chunks behind this one
+  for (int u = t + 1; u < AP_THREADS; ++u)
+    if (frac_gt(ibuf[u], ibuf[AP_THREADS + u], sn, sd)) { sn = ibuf[u]; sd = ibuf[AP_THREADS + u]; }
+  const long long G = n_gt[c];
+  double sum = 0.0;
+  ctp = before + cnt;
+  for (int i = last; i >= lo; --i) {                             // right to left: (sn, sd) = max_{j >= i} ctp_j / (j + 1)
+    if (frac_gt(ctp, i + 1, sn, sd)) { sn = ctp; sd = i + 1; }
+    if (keys[i] & 1ull) {
+      if (G > 0) sum += (double)sn / (double)((long long)sd * G);
+      --ctp;
+    }
+  }
+  dbuf[t] = sum;
+  __syncthreads();
+  for (int off = AP_THREADS >> 1; off > 0; off >>= 1) {
+    if (t < off) dbuf[t] += dbuf[t + off];
+    __syncthreads();
+  }
+  if (t == 0) ap[c] = G > 0 ? dbuf[0] : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+__global__ __launch_bounds__(AP_THREADS) void class_ap_voc_lds_kernel(const float* __restrict__ scores, const uint8_t* __restrict__ tpv,
+                                                                     const int32_t* __restrict__ n_gt, int n, int cols, int npad,
+                                                                     double* __restrict__ ap) {
+  __shared__ unsigned long long keys[VOC_LDS_MAX];
+  __shared__ int ibuf[2 * AP_THREADS];
+  __shared__ double dbuf[AP_THREADS];
+  class_ap_voc_body(scores, tpv, n_gt, n, cols, npad, keys, ibuf, dbuf, ap);
+}
+__global__ __launch_bounds__(AP_THREADS) void class_ap_voc_global_kernel(const float* __restrict__ scores, const uint8_t* __restrict__ tpv,
+                                                                        const int32_t* __restrict__ n_gt, int n, int cols, int npad,
+                                                                        unsigned long long* ws_keys, double* __restrict__ ap) {
+  __shared__ int ibuf[2 * AP_THREADS];
+  __shared__ double dbuf[AP_THREADS];
+  class_ap_voc_body(scores, tpv, n_gt, n, cols, npad, ws_keys + (size_t)blockIdx.x * npad, ibuf, dbuf, ap);
+}
+
+// a host copy of a CSR: starts at 0, never decreases, no image above `limit` entries; *total = its last value
+static int check_csr(const char* what, const int32_t* p, int64_t n_img, int limit, int64_t* total) {
+  VLFB_REQUIRE(p != nullptr, "ava_match_tp: the host copy of the %s CSR is required", what);
+  VLFB_REQUIRE(p[0] == 0, "ava_match_tp: the %s CSR starts at %d, not 0", what, p[0]);
+  for (int64_t i = 0; i < n_img; ++i) {
+    VLFB_REQUIRE(p[i + 1] >= p[i], "ava_match_tp: the %s CSR decreases at image %lld", what, (long long)i);
+    VLFB_REQUIRE(p[i + 1] - p[i] <= limit, "ava_match_tp: image %lld has %d %s rows, more than the %d one workgroup holds", (long long)i,
+                 p[i + 1] - p[i], what, limit);
+  }
+  *total = p[n_img];
+  return VLFB_OK;
+}
+
+}  // namespace vlfb
+
+int64_t vlfb_class_ap_voc_workspace_bytes_impl(int64_t n, int64_t cols) {
+  if (n < 1 || cols < 1 || n > VLFB_CLASS_AP_MAX_N) return -1;
+  return (int64_t)pad_pow2(n) * cols * 8;
+}
+
+extern "C" int vlfb_ava_match_tp(const float* scores, const double* det_box, int64_t n_rows, int64_t cols,
+                                 const int32_t* img_det_ptr, const int32_t* det_rows, const int32_t* img_gt_ptr,
+                                 const double* gt_box, const int32_t* gt_class, int64_t n_img, const int32_t* host_img_det_ptr,
+                                 const int32_t* host_img_gt_ptr, const uint8_t* class_mask, uint8_t* tp, int32_t* n_gt,
+                                 vlfb_stream_t stream) {
+  VLFB_REQUIRE(n_rows >= 1 && n_rows < (1ll << 31) && cols >= 1 && cols < (1ll << 31) && n_rows * cols < (1ll << 40),
+               "ava_match_tp: bad n_rows / cols %lld x %lld", (long long)n_rows, (long long)cols);
+  VLFB_REQUIRE(n_img >= 0 && n_img < (1ll << 31), "ava_match_tp: bad n_img %lld", (long long)n_img);
+  int64_t n_det = 0, n_gt_rows = 0;
+  if (int rc = check_csr("detection", host_img_det_ptr, n_img, VLFB_AVA_MAX_DET, &n_det)) return rc;
+  if (int rc = check_csr("ground-truth", host_img_gt_ptr, n_img, VLFB_AVA_MAX_GT, &n_gt_rows)) return rc;
+  VLFB_REQUIRE(n_det <= n_rows, "ava_match_tp: %lld detections named for a table of %lld rows", (long long)n_det, (long long)n_rows);
+  VLFB_REQUIRE(scores && class_mask && tp && n_gt, "ava_match_tp: scores, class_mask, tp and n_gt are required");
+  VLFB_REQUIRE(n_img == 0 || (img_det_ptr && img_gt_ptr), "ava_match_tp: the device copies of both CSRs are required");
+  VLFB_REQUIRE(n_det == 0 || (det_box && det_rows), "ava_match_tp: det_box and det_rows are required");
+  VLFB_REQUIRE(n_gt_rows == 0 || (gt_box && gt_class), "ava_match_tp: gt_box and gt_class are required");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long cells = (long long)n_rows * cols;
+  ava_fill_tp_kernel<<<(unsigned)std::min<long long>((cells + 255) / 256, 4096), 256, 0, s>>>(tp, cells);
+  ava_count_gt_kernel<<<(unsigned)cols, 256, 0, s>>>(gt_class, (int)n_gt_rows, class_mask, n_gt);
+  if (n_img > 0 && n_det > 0)
+    ava_match_kernel<<<(unsigned)n_img, AVA_THREADS, 0, s>>>(scores, det_box, (int)n_rows, (int)cols, img_det_ptr, det_rows, (int)n_det,
+                                                            img_gt_ptr, gt_box, gt_class, (int)n_gt_rows, class_mask, tp);
+  return check_launch("ava_match_tp");
+}
+
+extern "C" int vlfb_class_ap_voc(const float* scores, const uint8_t* tp, const int32_t* n_gt, int64_t n, int64_t cols, double* ap,
+                                 void* workspace, int64_t workspace_bytes, int flags, vlfb_stream_t stream) {
+  VLFB_REQUIRE(n >= 1 && n <= VLFB_CLASS_AP_MAX_N, "class_ap_voc: n = %lld outside 1..%d", (long long)n, VLFB_CLASS_AP_MAX_N);
+  VLFB_REQUIRE(cols >= 1 && cols < (1ll << 31), "class_ap_voc: bad cols %lld", (long long)cols);
+  VLFB_REQUIRE(scores != nullptr && tp != nullptr && n_gt != nullptr, "class_ap_voc: scores, tp and n_gt are required");
+  VLFB_REQUIRE(ap != nullptr, "class_ap_voc: ap is required");
+  VLFB_REQUIRE((flags & ~VLFB_CLASS_AP_FORCE_GLOBAL) == 0, "class_ap_voc: unknown flags 0x%x", flags);
+  const int npad = pad_pow2(n);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (npad <= VOC_LDS_MAX && !(flags & VLFB_CLASS_AP_FORCE_GLOBAL)) {
+    class_ap_voc_lds_kernel<<<(unsigned)cols, AP_THREADS, 0, s>>>(scores, tp, n_gt, (int)n, (int)cols, npad, ap);
+    return check_launch("class_ap_voc");
+  }
+  const int64_t need = vlfb_class_ap_voc_workspace_bytes_impl(n, cols);
+  if (workspace == nullptr || workspace_bytes < need)
+    return set_error(VLFB_ERR_WORKSPACE, "class_ap_voc: short workspace: %lld bytes given, %lld needed (n = %lld, cols = %lld)",
+                     (long long)workspace_bytes, (long long)need, (long long)n, (long long)cols);
+  class_ap_voc_global_kernel<<<(unsigned)cols, AP_THREADS, 0, s>>>(scores, tp, n_gt, (int)n, (int)cols, npad,
+                                                                  static_cast<unsigned long long*>(workspace), ap);
+  return check_launch("class_ap_voc");
+}

@@ -9,11 +9,15 @@ Differences that follow from reading once per period:
   * `top1` / `top5` of a log line are the error over the iterations since the previous line (the reference prints the
     last iteration's); the aggregated figures are the reference's (every iteration has the same batch size).
   * `Loss` is the last iteration's, from the engine's device loss ring.
-AVA's frame-mAP is absent: the reference does not ship the evaluator utils/ava_eval_helper.py imports
-(utils.ava_evaluation.*), so finalize_metrics raises NotImplementedError for cfg.DATASET == 'ava'.
+AVA's frame-mAP: the reference does not ship the evaluator its utils/ava_eval_helper.py imports
+(utils.ava_evaluation.*), so a MetricsCalculator built WITHOUT `ava_groundtruth` raises NotImplementedError in
+finalize_metrics for cfg.DATASET == 'ava'.  With it (read_csv's triple), the head's probabilities are appended to a device
+table inside the step, the caller reports every test iteration's metadata and boxes (add_ava_batch), and finalize_metrics
+scores the table with the PASCAL-VOC protocol at IoU 0.5 on the device (vlfb.metrics.ava_frame_ap).
 """
 from __future__ import absolute_import, division, print_function, unicode_literals
 
+import collections
 import datetime
 import logging
 
@@ -24,7 +28,22 @@ from core.config import config as cfg
 from vlfb import dist
 from vlfb.metrics import DeviceMeter
 
+# (the reference imports these names here as well)
+from utils.ava_eval_helper import evaluate_ava, evaluate_ava_from_files, read_csv, read_exclusions, read_labelmap  # noqa: F401
+
 logger = logging.getLogger(__name__)
+
+
+def get_ava_mini_groundtruth(full_groundtruth):
+    """the "mini" validation set: the entries of read_csv's three dictionaries whose second is a multiple of 4"""
+    mini = []
+    for part in full_groundtruth[:3]:
+        kept = collections.defaultdict(list)
+        for key in part.keys():
+            if int(key.split(',')[1]) % 4 == 0:
+                kept[key] = part[key]
+        mini.append(kept)
+    return mini
 
 
 def _dev(x, dtype):
@@ -70,7 +89,11 @@ class MetricsCalculator(object):
     reference's signature is the planned vlfb.engine.Engine here; `test_labels` is the int32 device tensor a
     test-mode net (no label blob) is metered against (Engine.attach_meter)."""
 
-    def __init__(self, engine, split, video_idx_to_name=None, total_num_boxes=None, test_labels=None):
+    def __init__(self, engine, split, video_idx_to_name=None, total_num_boxes=None, test_labels=None, ava_groundtruth=None,
+                 excluded_keys=None, class_whitelist=None, categories=None, ava_table_rows=None):
+        """ava_groundtruth: read_csv's (boxes, labels, scores) -- with it an AVA config is scored (frame-mAP);
+        excluded_keys / class_whitelist / categories: read_exclusions' and read_labelmap's results; ava_table_rows: rows of
+        the score table (default: every row ceil(TEST.DATASET_SIZE / TEST.BATCH_SIZE) iterations issue, padding included)"""
         self.model = self.engine = engine
         self.split = split
         self.video_idx_to_name = video_idx_to_name
@@ -84,8 +107,19 @@ class MetricsCalculator(object):
             # (tools/test_net.py / train_net.py set NUM_TEST_CLIPS from _FINAL_EVAL / _DURING_TRAINING before they test)
             self.num_test_clips = cfg.CHARADES.get("NUM_TEST_CLIPS", cfg.CHARADES.NUM_TEST_CLIPS_DURING_TRAINING)
         self.meter = None
+        self.ava_groundtruth = ava_groundtruth
+        self.excluded_keys = set(excluded_keys) if excluded_keys else set()
+        self.class_whitelist = set(class_whitelist) if class_whitelist else None
+        self.categories = categories
         from vlfb.engine import LossStep
         heads = [st for st in engine.steps if isinstance(st, LossStep) and st.prob is not None]
+        if cfg.DATASET == 'ava' and ava_groundtruth is not None and heads and split != 'train':
+            cols, self.batch_rows = heads[0].cols, heads[0].rows
+            if ava_table_rows is None:
+                per_rank = max(cfg.TEST.BATCH_SIZE // dist.world_size(), 1)
+                ava_table_rows = -(-max(cfg.TEST.DATASET_SIZE // dist.world_size(), 1) // per_rank) * self.batch_rows
+            self.meter = DeviceMeter("ava", cols, n_items=int(ava_table_rows), device=engine.device)
+            engine.attach_meter(self.meter, labels=test_labels)
         if cfg.DATASET != 'ava' and heads:
             cols, self.batch_rows = heads[0].cols, heads[0].rows
             if cfg.MODEL.MULTI_LABEL:
@@ -106,8 +140,26 @@ class MetricsCalculator(object):
         self._last = (0, 0, 0)                       # hits@1, hits@5, rows at the previous read
         self.avg_loss = self.avg_err = self.avg_err5 = float('nan')
         self.full_map = 0.0
+        self._ava_pos = 0                            # table row the next test iteration starts at
+        self._ava_rows, self._ava_keys, self._ava_boxes = [], [], []
         if self.meter is not None:
             self.meter.reset()
+
+    def add_ava_batch(self, metadata, original_boxes):
+        """AVA, once per test iteration: metadata [r][2] = (video index, second) and original_boxes [r][5] =
+        (batch index, x1, y1, x2, y2) of the r REAL RoIs of the iteration.  The step issued the planned number of rows;
+        the rows behind r are padding and are never named to the evaluator."""
+        assert self.meter is not None and self.meter.kind == "ava", "add_ava_batch needs ava_groundtruth= on an AVA config"
+        metadata = np.asarray(metadata).reshape(-1, 2)
+        boxes = np.asarray(original_boxes, np.float64).reshape(-1, 5)
+        r = metadata.shape[0]
+        assert boxes.shape[0] == r and r <= self.batch_rows, (r, boxes.shape, self.batch_rows)
+        self._ava_rows.append(self._ava_pos + np.arange(r, dtype=np.int64))
+        for m in metadata:
+            video = self.video_idx_to_name[int(np.round(m[0]))]
+            self._ava_keys.append(video + ',' + '%04d' % int(np.round(m[1])))
+        self._ava_boxes.append(boxes[:, 1:5])
+        self._ava_pos += self.batch_rows
 
     def _read_topk(self):
         """(period err, period err5, aggregated err, aggregated err5) from ONE read, summed over ranks"""
@@ -164,10 +216,36 @@ class MetricsCalculator(object):
 
     def finalize_metrics(self, is_train=False, name='latest'):
         """the final figures: mAP of the merged table (Charades), or the aggregated top-1 / top-5 error"""
-        if cfg.DATASET == 'ava':
+        if cfg.DATASET == 'ava' and self.ava_groundtruth is None:
             raise NotImplementedError(
                 "AVA frame-mAP: the reference does not ship its evaluator (utils/ava_eval_helper.py imports "
                 "utils.ava_evaluation.*, which is absent), so there is nothing to compute it with")
+        if cfg.DATASET == 'ava':
+            self.full_map = 0.0
+            if is_train or self.meter is None:
+                return
+            # one add_ava_batch per forward pass: a missed or doubled call would shift every later row
+            cursor = self.meter.counters()[2]
+            assert self._ava_pos == cursor, "add_ava_batch accounted for %d table rows, the steps issued %d" % (self._ava_pos, cursor)
+            rows = np.concatenate(self._ava_rows) if self._ava_rows else np.zeros(0, np.int64)
+            boxes = np.concatenate(self._ava_boxes) if self._ava_boxes else np.zeros((0, 4))
+            keys = list(self._ava_keys)
+            if dist.world_size() > 1:
+                # every rank holds the rows it tested: gather the tables once, shift every rank's row numbers
+                import torch.distributed as td
+                from vlfb.metrics import ava_frame_ap
+                table = dist.gather_rows(self.meter.table[:self._ava_pos])
+                parts = [None] * dist.world_size()
+                td.all_gather_object(parts, (rows, keys, boxes))
+                rows = np.concatenate([p[0] + i * self._ava_pos for i, p in enumerate(parts)])
+                keys = [k for p in parts for k in p[1]]
+                boxes = np.concatenate([p[2] for p in parts])
+                self.results = ava_frame_ap(table.contiguous(), rows, keys, boxes, self.ava_groundtruth, self.excluded_keys,
+                                            self.class_whitelist)
+            else:
+                self.results = self.meter.finalize(rows, keys, boxes, self.ava_groundtruth, self.excluded_keys, self.class_whitelist)
+            self.full_map = self.results["mean_ap"]
+            return
         if self.meter is None:
             self.full_map = 0.0
             return
@@ -214,7 +292,10 @@ class MetricsCalculator(object):
         if total_iters is None:
             total_iters = cfg.SOLVER.MAX_ITER
         if cfg.MODEL.MULTI_LABEL:
-            print('* {} testing finished #iters [{}|{}]: mAP: {:.3f}'.format('', model_iter + 1, total_iters, self.full_map))
+            info = ''
+            if self.meter is not None and self.meter.kind == "ava" and cfg.AVA.get("DETECTION_SCORE_THRESH") is not None:
+                info = 'Box@%.5f ' % cfg.AVA.DETECTION_SCORE_THRESH
+            print('* {} testing finished #iters [{}|{}]: mAP: {:.3f}'.format(info, model_iter + 1, total_iters, self.full_map))
         else:
             print('* Finished #iters [{}|{}]: top1: {:.3f} top5: {:.3f}'.format(
                 model_iter + 1, total_iters, 100.0 - self.avg_err, 100.0 - self.avg_err5))

@@ -3163,11 +3163,17 @@ class Engine(object):
                 raise hip.VlfbError("attach_meter: the planned net has no head that produces probabilities")
             for st in heads:
                 want = "topk" if st.kernel == "vlfb_softmax_ce" else "map"
-                if meter.kind != want or meter.cols != st.cols:
+                # (an "ava" meter is the table of a "map" meter in append mode: the same kernel behind the same head)
+                if (meter.kind != want and not (meter.kind == "ava" and want == "map")) or meter.cols != st.cols:
                     raise hip.VlfbError("attach_meter: a %r meter of %d classes on a %s head of %d classes (needs %r)" % (
                         meter.kind, meter.cols, st.kernel, st.cols, want))
                 if st.labels is None:
                     n = st.rows * (1 if want == "topk" else st.cols)
+                    if meter.kind == "ava" and labels is None:
+                        # scored against the annotation files, not against a label blob: the merge kernel reads zeros
+                        # (a net has one RoI head; the buffer is sized for the head it is made for)
+                        assert len(heads) == 1, "an 'ava' meter needs `labels` when the net has %d heads" % len(heads)
+                        labels = torch.zeros(n, dtype=torch.int32, device=self.device)
                     if labels is None:               # the fed `labels*` input blob nothing in a test-mode graph reads
                         fed = [b for k, b in self.env.items() if str(k).startswith("labels") and b.root.tensor is not None]
                         labels = fed[0].root.tensor if len(fed) == 1 else None

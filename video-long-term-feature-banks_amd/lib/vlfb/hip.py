@@ -178,6 +178,8 @@ _SIGS = {
     "vlfb_action_topk_hits": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, C.c_int, _P, _P]),
     "vlfb_scores_merge_max": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P]),
     "vlfb_class_ap_auc": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, C.c_int, _P]),
+    "vlfb_ava_match_tp": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "vlfb_class_ap_voc": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _I64, C.c_int, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
@@ -295,9 +297,12 @@ def conv_plan(d):
     return buf.value.decode()
 
 
-WS_CONV, WS_MAXPOOL_ARGMAX, WS_FBO_ATTN_BWD, WS_ATTN_SCORES, WS_BN, WS_CLASS_AP = 0, 1, 2, 3, 4, 5
-CLASS_AP_FORCE_GLOBAL = 1                           # vlfb_class_ap_auc flags: sort in the global workspace whatever n is
+WS_CONV, WS_MAXPOOL_ARGMAX, WS_FBO_ATTN_BWD, WS_ATTN_SCORES, WS_BN, WS_CLASS_AP, WS_CLASS_AP_VOC = 0, 1, 2, 3, 4, 5, 6
+CLASS_AP_FORCE_GLOBAL = 1                           # vlfb_class_ap_auc / _voc flags: sort in the global workspace whatever n is
 CLASS_AP_LDS_MAX = 8192                             # largest n vlfb_class_ap_auc sorts in LDS
+CLASS_AP_VOC_LDS_MAX = 4096                         # ... and vlfb_class_ap_voc, whose sort key is 64 bits wide
+CLASS_AP_MAX_N = 1 << 20                            # vlfb.h VLFB_CLASS_AP_MAX_N
+AVA_MAX_DET, AVA_MAX_GT = 128, 128                  # vlfb.h VLFB_AVA_MAX_DET / _GT: rows of one image vlfb_ava_match_tp holds
 
 
 def query_workspace(op, arg):

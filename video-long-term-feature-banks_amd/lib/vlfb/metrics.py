@@ -9,6 +9,9 @@ constant arguments that sit inside the step and add into device state; `read()` 
                max at (stream position % n_items) -- clip c of video i arrives at position i + c * n_items, which is
                aggregate_predictions_from_clips (metrics.py:165-186) done while the clips arrive -- and from which
                `read()` computes mAP / wAP / ROC-AUC (mean_ap_metric, :444-482)
+  kind "ava"   the RoI head of AVA: the same table in append mode (n_items >= every row the test issues, padding rows of
+               ragged batches included); `finalize()` builds the image index from the host-side metadata, and
+               vlfb_ava_match_tp + vlfb_class_ap_voc turn table, boxes and ground truth into the frame-mAP (ava_frame_ap)
 
 Tie rule of top-k: rank = #{j : s_j > s_label} + #{j < label : s_j == s_label}, hit iff rank < k (include/vlfb.h).
 """
@@ -46,7 +49,7 @@ class DeviceMeter(object):
     workspace.  `update` issues kernels on the current stream and returns nothing; `read` synchronises."""
 
     def __init__(self, kind, cols, ks=(1, 5), n_items=None, total_rows=0, device=None):
-        assert kind in ("topk", "map"), kind
+        assert kind in ("topk", "map", "ava"), kind
         self.kind, self.cols = kind, int(cols)
         self.ks = tuple(int(k) for k in ks)
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
@@ -56,7 +59,7 @@ class DeviceMeter(object):
             if not (1 <= len(self.ks) <= 4 and all(1 <= k <= self.cols for k in self.ks)):
                 raise hip.VlfbError("DeviceMeter: ks = %r needs 1..4 values within 1..cols = %d" % (self.ks, self.cols))
         elif self.n_items < 1:
-            raise hip.VlfbError("DeviceMeter: a 'map' meter needs n_items >= 1 (videos, or rows when nothing is merged)")
+            raise hip.VlfbError("DeviceMeter: a %r meter needs n_items >= 1 (videos, or rows when nothing is merged)" % kind)
         self._ks = hip.ks_array(self.ks)
         # layout (bytes): hits int64[5] | cursor int64 | mismatches int32 (+pad) | ap f64[cols] | auc f64[cols] |
         #                 n_pos int32[cols] | table f32[n][cols] | labels u8[n][cols] | sort workspace
@@ -67,6 +70,8 @@ class DeviceMeter(object):
         if kind == "map":
             self.ws_bytes = hip.query_workspace(hip.WS_CLASS_AP, (n, c)) if n > hip.CLASS_AP_LDS_MAX else 0
             sizes += [("table", 4 * n * c), ("labels", n * c), ("ws", self.ws_bytes)]
+        elif kind == "ava":                          # (tp, ap, n_gt and the sort workspace belong to one ava_frame_ap call)
+            sizes += [("table", 4 * n * c), ("labels", n * c)]
         for name, nbytes in sizes:
             off[name] = at
             at = _align(at + nbytes)
@@ -82,12 +87,15 @@ class DeviceMeter(object):
             self.table = view("table", 4 * n * c, torch.float32).view(n, c)
             self.labels = view("labels", n * c, torch.uint8).view(n, c)
             self.ws = self.buf[off["ws"]:off["ws"] + self.ws_bytes] if self.ws_bytes else None
+        elif kind == "ava":
+            self.table = view("table", 4 * n * c, torch.float32).view(n, c)
+            self.labels = view("labels", n * c, torch.uint8).view(n, c)
         self.reset()
 
     def reset(self):
         """asynchronous: fills on the current stream"""
         self.head.zero_()
-        if self.kind == "map":
+        if self.kind in ("map", "ava"):
             self.table.fill_(float("-inf"))
             self.labels.fill_(255)
 
@@ -127,6 +135,8 @@ class DeviceMeter(object):
         """the only call that synchronises.  `hits` / `rows`: counters to report instead of this meter's own (the sums
         over data-parallel ranks, utils.metrics.MetricsCalculator)"""
         own_hits, own_rows, cursor, mismatches = self.counters()
+        if self.kind == "ava":
+            raise hip.VlfbError("DeviceMeter.read: an 'ava' meter is scored by finalize(), which needs the host-side metadata")
         if self.kind == "topk":
             hits = own_hits if hits is None else hits
             rows = own_rows if rows is None else rows
@@ -141,6 +151,120 @@ class DeviceMeter(object):
         mean_auc, mean_ap, mean_wap, all_aps = summarize_ap(ap, auc, n_pos)
         return {"mean_ap": mean_ap, "mean_wap": mean_wap, "mean_auc": mean_auc, "all_aps": all_aps, "rows": n,
                 "rows_seen": cursor, "label_mismatches": mismatches}
+
+    def finalize(self, det_rows, det_keys, det_boxes, groundtruth, excluded_keys=(), class_whitelist=None, flags=0):
+        """kind "ava": the frame-mAP of the table rows `det_rows` (never a padding row) whose image keys and boxes
+        (x1, y1, x2, y2) the host kept while the rows were issued; see ava_frame_ap.  Synchronises."""
+        assert self.kind == "ava", self.kind
+        _, _, cursor, _ = self.counters()
+        if cursor > self.n_items:
+            raise hip.VlfbError("DeviceMeter.finalize: %d rows were issued into a table of %d: early rows were overwritten"
+                                % (cursor, self.n_items))
+        det_rows = np.asarray(det_rows, np.int64).reshape(-1)
+        if det_rows.size and (det_rows.min() < 0 or det_rows.max() >= cursor):
+            raise hip.VlfbError("DeviceMeter.finalize: table row %d named, %d rows issued" % (int(det_rows.max()), cursor))
+        if cursor < 1:
+            raise hip.VlfbError("DeviceMeter.finalize: no prediction has been issued yet")
+        r = ava_frame_ap(self.table[:cursor], det_rows, det_keys, det_boxes, groundtruth, excluded_keys, class_whitelist, flags)
+        r["rows_seen"] = cursor
+        return r
+
+
+def ava_image_index(det_rows, det_keys, det_boxes, groundtruth, excluded_keys=()):
+    """The image index of one evaluation, on the host (integer keys and annotation boxes, no model output): images = the
+    ground-truth keys in their order, then the detection keys not among them, minus `excluded_keys`; detections with
+    x2 < x1 or y2 < y1 are dropped (the evaluator's _remove_invalid_boxes).  groundtruth = read_csv's (boxes, labels[,
+    scores]): boxes[key] = [[y1, x1, y2, x2], ...], one entry per (box, label) in file order.
+    -> dict(keys, img_det_ptr, det_rows, det_boxes [n_det][4], img_gt_ptr, gt_box [n_gt][4] as (x1, y1, x2, y2), gt_class)"""
+    det_rows = np.asarray(det_rows, np.int64).reshape(-1)
+    det_boxes = np.asarray(det_boxes, np.float64).reshape(-1, 4)
+    assert len(det_keys) == det_rows.shape[0] == det_boxes.shape[0], (len(det_keys), det_rows.shape, det_boxes.shape)
+    excluded_keys = set(excluded_keys) if excluded_keys else set()
+    gt_boxes, gt_labels = groundtruth[0], groundtruth[1]
+    index, keys = {}, []
+    for key in gt_boxes:
+        if key not in excluded_keys and key not in index:
+            index[key] = len(keys)
+            keys.append(key)
+    n_gt_img = len(keys)
+    img = np.empty(det_rows.shape[0], np.int64)
+    for i, key in enumerate(det_keys):
+        if key in excluded_keys:
+            img[i] = -1
+            continue
+        at = index.get(key)
+        if at is None:
+            at = index[key] = len(keys)
+            keys.append(key)
+        img[i] = at
+    valid = (img >= 0) & (det_boxes[:, 2] >= det_boxes[:, 0]) & (det_boxes[:, 3] >= det_boxes[:, 1])
+    sel = np.flatnonzero(valid)
+    sel = sel[np.argsort(img[sel], kind="stable")]             # per image, in the order the rows were issued
+    n_img = len(keys)
+    img_det_ptr = np.zeros(n_img + 1, np.int64)
+    np.cumsum(np.bincount(img[sel], minlength=n_img), out=img_det_ptr[1:])
+    gb, gc = [], []
+    img_gt_ptr = np.zeros(n_img + 1, np.int64)
+    for i in range(n_gt_img):
+        key = keys[i]
+        assert len(gt_boxes[key]) == len(gt_labels[key]), key
+        gb.extend(gt_boxes[key])
+        gc.extend(gt_labels[key])
+        img_gt_ptr[i + 1] = len(gc)
+    img_gt_ptr[n_gt_img + 1:] = len(gc)
+    gb = np.asarray(gb, np.float64).reshape(-1, 4)[:, [1, 0, 3, 2]]
+    return {"keys": keys, "img_det_ptr": img_det_ptr.astype(np.int32), "det_rows": det_rows[sel].astype(np.int32),
+            "det_boxes": det_boxes[sel], "img_gt_ptr": img_gt_ptr.astype(np.int32), "gt_box": np.ascontiguousarray(gb),
+            "gt_class": np.asarray(gc, np.int32).reshape(-1)}
+
+
+def ava_frame_ap(table, det_rows, det_keys, det_boxes, groundtruth, excluded_keys=(), class_whitelist=None, flags=0,
+                 return_tp=False):
+    """AVA frame-mAP (PASCAL VOC at IoU 0.5; include/vlfb.h, "AVA frame-mAP") of a device score table fp32 [n_rows][cols]:
+    class id = column + 1, `det_rows` / `det_keys` / `det_boxes` name the table rows that are detections, their image
+    keys and their boxes (x1, y1, x2, y2).  The index is built on the host (ava_image_index) and uploaded; the two kernels
+    run on the current stream; ap and n_gt are read once.  class_whitelist: class ids that are scored (None = all).
+    -> dict(mean_ap, ap [cols], n_gt [cols], class_mask, images, detections[, tp])"""
+    assert table.dim() == 2 and table.dtype == torch.float32 and table.is_contiguous() and table.is_cuda
+    n_rows, cols = int(table.shape[0]), int(table.shape[1])
+    ix = ava_image_index(det_rows, det_keys, det_boxes, groundtruth, excluded_keys)
+    for name, limit, what in (("img_det_ptr", hip.AVA_MAX_DET, "detections"), ("img_gt_ptr", hip.AVA_MAX_GT, "ground-truth rows")):
+        per = np.diff(ix[name])
+        if per.size and per.max() > limit:
+            i = int(np.argmax(per))
+            raise hip.VlfbError("ava_frame_ap: image %r has %d %s, more than the %d one workgroup holds"
+                                % (ix["keys"][i], int(per[i]), what, limit))
+    mask = np.zeros(cols, np.uint8)
+    if class_whitelist is None:
+        mask[:] = 1
+    else:
+        for cid in class_whitelist:
+            if 1 <= int(cid) <= cols:
+                mask[int(cid) - 1] = 1
+    boxes = np.zeros((n_rows, 4), np.float64)
+    boxes[ix["det_rows"]] = ix["det_boxes"]
+    dev = table.device
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else None
+    d_box, d_dptr, d_rows, d_gptr = up(boxes), up(ix["img_det_ptr"]), up(ix["det_rows"]), up(ix["img_gt_ptr"])
+    d_gbox, d_gcls, d_mask = up(ix["gt_box"]), up(ix["gt_class"]), up(mask)
+    tp = torch.empty((n_rows, cols), dtype=torch.uint8, device=dev)
+    n_gt = torch.empty(cols, dtype=torch.int32, device=dev)
+    ap = torch.empty(cols, dtype=torch.float64, device=dev)
+    n_img = len(ix["keys"])
+    hip.call("vlfb_ava_match_tp", hip.ptr(table), hip.ptr(d_box), n_rows, cols, hip.ptr(d_dptr), hip.ptr(d_rows), hip.ptr(d_gptr),
+             hip.ptr(d_gbox), hip.ptr(d_gcls), n_img, ix["img_det_ptr"].ctypes.data, ix["img_gt_ptr"].ctypes.data, hip.ptr(d_mask),
+             hip.ptr(tp), hip.ptr(n_gt))
+    ws_bytes = hip.query_workspace(hip.WS_CLASS_AP_VOC, (n_rows, cols)) \
+        if (n_rows > hip.CLASS_AP_VOC_LDS_MAX or flags & hip.CLASS_AP_FORCE_GLOBAL) else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    hip.call("vlfb_class_ap_voc", hip.ptr(table), hip.ptr(tp), hip.ptr(n_gt), n_rows, cols, hip.ptr(ap), hip.ptr(ws), ws_bytes, flags)
+    ap_h, n_gt_h = ap.cpu().numpy(), n_gt.cpu().numpy()
+    keep = (mask == 1) & (n_gt_h > 0)
+    out = {"mean_ap": float(np.mean(ap_h[keep])) if keep.any() else float("nan"), "ap": ap_h, "n_gt": n_gt_h,
+           "class_mask": mask, "images": n_img, "detections": int(ix["det_rows"].shape[0])}
+    if return_tp:
+        out["tp"] = tp.cpu().numpy()
+    return out
 
 
 def action_topk_hits(verb, noun, verb_labels, noun_labels, ks=(1, 5), prior=None):
