@@ -600,6 +600,48 @@ int vlfb_clip_preprocess(const vlfb_clip_desc* d, const uint8_t* frames, const i
                          const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, void* dst,
                          int dst_dtype, vlfb_stream_t stream);
 
+/* Colour augmentation of the train clip (cfg.TRAIN.USE_COLOR_AUGMENTATION: color_augmentation_list,
+ * lib/datasets/data_input_helper.py:142-151; color_jitter_list / brightness_list / contrast_list / saturation_list /
+ * lighting_list, lib/datasets/image_processor.py:252-336), between x / 255 and the normalisation of the walk above.
+ * The host draws the op order, the blend factors and the lighting offsets; two kernels apply them.
+ *
+ * vlfb_clip_channel_sums: sums int64 [frames][VLFB_CLIP_SUM_BANDS][3] = the integer sums of the uint8 B, G, R values of
+ * the pixels vlfb_clip_preprocess reads (same geometry, flip and fixed-point resize; dst fields of the descriptor are
+ * not read), per frame and per band of crop rows [b * crop_h / 8, (b + 1) * crop_h / 8) (integer division; an empty
+ * band gives zeros).  Every slot is written: the caller need not clear `sums`.  One workgroup per (band, frame), no
+ * atomics: integers, so the sums do not depend on the launch geometry.  crop_h * crop_w must be below 2^31 (a thread's
+ * 32-bit counters).
+ *
+ * vlfb_clip_preprocess_color: per pixel, in fp32, with (b, g, r) = x / 255 of the source channels, for i < n_ops:
+ *   grey = 0.299f * r + 0.587f * g + 0.114f * b  of the pixel's current value
+ *   VLFB_COLOR_BRIGHTNESS  v = v * alpha[i]
+ *   VLFB_COLOR_SATURATION  v = v * alpha[i] + grey * (1 - alpha[i])
+ *   VLFB_COLOR_CONTRAST    v = v * alpha[i] + M * (1 - alpha[i]),  M = m * (the alphas of the brightness ops before it),
+ *                          m = (float)((0.299 * S_R + 0.587 * S_G + 0.114 * S_B) / (255 * crop_h * crop_w)) in double, S_c =
+ *                          the frame's 8 band sums added in band order (the reference takes np.mean of the grey image at
+ *                          that point of the chain; a saturation blend leaves a pixel's grey value unchanged up to
+ *                          rounding because the weights add to one, so one pass over the un-augmented window serves)
+ * then v += light[c] (AlexNet-style PCA lighting, per SOURCE channel), (v - mean[c]) / std[c], channel swap and store as
+ * vlfb_clip_preprocess does.  n_ops = 0 and light = 0 give vlfb_clip_preprocess's output bit for bit.  `sums` may be NULL
+ * when no contrast op is present.  An op code outside 0..2 or listed twice, and n_ops outside 0..3, are rejected. */
+#define VLFB_CLIP_SUM_BANDS 8
+#define VLFB_COLOR_BRIGHTNESS 0
+#define VLFB_COLOR_CONTRAST 1
+#define VLFB_COLOR_SATURATION 2
+typedef struct vlfb_clip_color {
+  int32_t n_ops;        /* 0..3 jitter ops, applied in this order */
+  int32_t op[3];        /* 0 brightness, 1 contrast, 2 saturation */
+  float   alpha[3];     /* blend factor of op[i] */
+  float   light[3];     /* PCA offset per SOURCE channel (B, G, R), added after the ops */
+} vlfb_clip_color;
+int vlfb_clip_channel_sums(const vlfb_clip_desc* d, const uint8_t* frames, const int32_t* xofs,
+                           const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int64_t* sums,
+                           vlfb_stream_t stream);
+int vlfb_clip_preprocess_color(const vlfb_clip_desc* d, const vlfb_clip_color* c, const uint8_t* frames,
+                               const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs,
+                               const int16_t* ycoef, const int64_t* sums, void* dst, int dst_dtype,
+                               vlfb_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics on the device.  Replace the host meter of lib/utils/metrics.py, which fetches `pred` and
  * `labels` from every GPU every iteration (get_multi_gpu_outputs, :514-540), and tools/evaluate_actions.py.

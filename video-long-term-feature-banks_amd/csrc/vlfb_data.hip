@@ -9,6 +9,9 @@
 // cv::resize does and the kernel does integer arithmetic only, so the result does not depend on
 // floating-point contraction or rounding modes.  Built with -ffp-contract=off for the fp32
 // normalisation tail (same operation order as the NumPy code: x / 255, - mean, / std).
+//
+// TRAIN.USE_COLOR_AUGMENTATION adds two kernels beside it: an integer per-frame channel-sum pass (the contrast
+// jitter blends with the frame's grey mean) and the same walk with the colour chain before the normalisation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -72,10 +75,178 @@ __global__ void clip_preprocess_kernel(ClipP p, T* __restrict__ dst) {
   }
 }
 
+// ---- colour augmentation (TRAIN.USE_COLOR_AUGMENTATION): data_input_helper.py:120-151 color_augmentation_list,
+// image_processor.py:252-336 lighting_list / blend / grayscale / saturation_list / brightness_list / contrast_list ----
+
+struct ColorP {
+  int n_ops, op[3];
+  float alpha[3], light[3];
+  const int64_t* sums;    // [T][VLFB_CLIP_SUM_BANDS][3] of clip_channel_sums_kernel, NULL without a contrast op
+};
+
+// One block per (band, frame): the integer B, G, R sums of the uint8 pixels clip_preprocess_kernel reads in crop rows
+// [band * crop_h / 8, (band + 1) * crop_h / 8).  Integers, so the result does not depend on the block size or on the
+// order of the reduction.  A thread takes every 256th pixel of the band: the wrapper bounds crop_h * crop_w so that
+// its 32-bit counters cannot wrap; from the wave reduction on the sums are 64-bit.
+constexpr int SUM_THREADS = 256;
+
+__global__ void __launch_bounds__(SUM_THREADS) clip_channel_sums_kernel(ClipP p, int64_t* __restrict__ sums) {
+  const int band = blockIdx.x, t = blockIdx.y;
+  const int r0 = (int)((long long)band * p.crop_h / VLFB_CLIP_SUM_BANDS);
+  const int r1 = (int)((long long)(band + 1) * p.crop_h / VLFB_CLIP_SUM_BANDS);
+  const long long n = (long long)(r1 - r0) * p.crop_w;
+  const uint8_t* frame = p.src + (long long)t * p.Hs * p.Ws * 3;
+  uint32_t acc[3] = {0u, 0u, 0u};
+  for (long long i = threadIdx.x; i < n; i += SUM_THREADS) {
+    const int x = (int)(i % p.crop_w);
+    const int y = r0 + (int)(i / p.crop_w);
+    const int xs = p.flip ? p.x0 - x : p.x0 + x;
+    const int ys = p.y0 + y;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] += (uint32_t)resized_u8(p, frame, ys, xs, c);
+  }
+  __shared__ unsigned long long part[SUM_THREADS / 64][3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    unsigned long long v = acc[c];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) part[wave][c] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t* out = sums + ((long long)t * VLFB_CLIP_SUM_BANDS + band) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      unsigned long long v = 0;
+      for (int w = 0; w < SUM_THREADS / 64; ++w) v += part[w][c];
+      out[c] = (int64_t)v;
+    }
+  }
+}
+
+// The walk of clip_preprocess_kernel with the frame on grid axis y and the colour chain between / 255 and the
+// normalisation.  fp32 throughout, one rounding per operation (-ffp-contract=off), in the order the NumPy code applies them.
+template <typename T>
+__global__ void clip_preprocess_color_kernel(ClipP p, ColorP q, T* __restrict__ dst) {
+  const int t = blockIdx.y;
+  // grey mean of the frame as the contrast op meets it: the exact mean of the un-augmented window, times the alphas of
+  // the brightness ops before it (a saturation blend keeps a pixel's grey value: the three weights add to one)
+  float grey_mean = 0.0f;
+  if (q.sums) {
+    int64_t s[3] = {0, 0, 0};
+    for (int b = 0; b < VLFB_CLIP_SUM_BANDS; ++b)
+      for (int c = 0; c < 3; ++c) s[c] += q.sums[((long long)t * VLFB_CLIP_SUM_BANDS + b) * 3 + c];
+    const double num = 0.299 * (double)s[2] + 0.587 * (double)s[1] + 0.114 * (double)s[0];
+    grey_mean = (float)(num / (255.0 * (double)((long long)p.crop_h * p.crop_w)));
+    for (int k = 0; k < q.n_ops && q.op[k] != VLFB_COLOR_CONTRAST; ++k)
+      if (q.op[k] == VLFB_COLOR_BRIGHTNESS) grey_mean = grey_mean * q.alpha[k];
+  }
+  const uint8_t* frame = p.src + (long long)t * p.Hs * p.Ws * 3;
+  const long long total = (long long)p.crop_h * p.crop_w;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % p.crop_w);
+    const int y = (int)(i / p.crop_w);
+    const int xs = p.flip ? p.x0 - x : p.x0 + x;
+    const int ys = p.y0 + y;
+    T* d = dst + ((long long)(t * p.crop_h + y) * p.wtot + p.wl + x) * p.c_pad;
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (float)resized_u8(p, frame, ys, xs, c) / 255.0f;
+    for (int k = 0; k < q.n_ops; ++k) {
+      const float a = q.alpha[k];
+      if (q.op[k] == VLFB_COLOR_BRIGHTNESS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = v[c] * a;
+      } else {
+        float other = grey_mean;
+        if (q.op[k] == VLFB_COLOR_SATURATION) other = 0.299f * v[2] + 0.587f * v[1] + 0.114f * v[0];
+        const float rest = other * (1.0f - a);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = v[c] * a + rest;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float w = v[c] + q.light[c];
+      w = w - p.mean[c];
+      w = w / p.stdv[c];
+      Elem<T>::st(d + (p.to_rgb ? 2 - c : c), w);
+    }
+  }
+}
+
+// argument checks and kernel parameters shared by the two colour entry points (`with_dst`: the destination row too)
+int clip_params(const char* what, const vlfb_clip_desc* d, const uint8_t* frames, const int32_t* xofs, const int16_t* xcoef,
+                const int32_t* yofs, const int16_t* ycoef, bool with_dst, ClipP* p) {
+  VLFB_REQUIRE(d && frames, "%s: NULL buffer", what);
+  VLFB_REQUIRE(d->frames > 0 && d->src_h > 0 && d->src_w > 0 && d->crop_h > 0 && d->crop_w > 0, "%s: empty geometry", what);
+  VLFB_REQUIRE(d->frames <= 65535, "%s: more than 65535 frames", what);
+  const bool resize = d->resized_h != d->src_h || d->resized_w != d->src_w;
+  VLFB_REQUIRE(!resize || (xofs && xcoef && yofs && ycoef), "%s: resize tables are required", what);
+  VLFB_REQUIRE(d->y0 >= 0 && d->y0 + d->crop_h <= d->resized_h && d->x0 >= 0 && d->x0 < d->resized_w &&
+                   (d->flip ? d->x0 - (d->crop_w - 1) >= 0 : d->x0 + d->crop_w <= d->resized_w),
+               "%s: crop window leaves the resized frame", what);
+  // one thread of the sums kernel adds at most ceil(crop_h * crop_w / 256) values of at most 255 into 32 bits
+  VLFB_REQUIRE((long long)d->crop_h * d->crop_w <= (1ll << 31) - 1, "%s: crop window of more than 2^31 - 1 pixels", what);
+  if (with_dst)
+    VLFB_REQUIRE(d->c_pad >= 3 && d->w_left >= 0 && d->w_total >= d->w_left + d->crop_w, "%s: bad destination row", what);
+  p->src = frames; p->xofs = xofs; p->xcoef = xcoef; p->yofs = yofs; p->ycoef = ycoef;
+  p->T = d->frames; p->Hs = d->src_h; p->Ws = d->src_w; p->Hr = d->resized_h; p->Wr = d->resized_w;
+  p->resize = resize ? 1 : 0;
+  p->crop_h = d->crop_h; p->crop_w = d->crop_w; p->y0 = d->y0; p->x0 = d->x0; p->flip = d->flip;
+  for (int c = 0; c < 3; ++c) { p->mean[c] = d->mean[c]; p->stdv[c] = d->std[c]; }
+  p->to_rgb = d->to_rgb; p->wl = d->w_left; p->wtot = d->w_total; p->c_pad = d->c_pad;
+  return VLFB_OK;
+}
+
 }  // namespace
 }  // namespace vlfb
 
 using namespace vlfb;
+
+extern "C" int vlfb_clip_channel_sums(const vlfb_clip_desc* d, const uint8_t* frames, const int32_t* xofs,
+                                      const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,
+                                      int64_t* sums, vlfb_stream_t stream) {
+  ClipP p;
+  const int rc = clip_params("clip_channel_sums", d, frames, xofs, xcoef, yofs, ycoef, false, &p);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(sums, "clip_channel_sums: NULL sums");
+  hipLaunchKernelGGL(clip_channel_sums_kernel, dim3(VLFB_CLIP_SUM_BANDS, p.T), dim3(SUM_THREADS), 0, (hipStream_t)stream, p, sums);
+  return check_launch("clip_channel_sums");
+}
+
+extern "C" int vlfb_clip_preprocess_color(const vlfb_clip_desc* d, const vlfb_clip_color* c, const uint8_t* frames,
+                                          const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs,
+                                          const int16_t* ycoef, const int64_t* sums, void* dst, int dst_dtype,
+                                          vlfb_stream_t stream) {
+  ClipP p;
+  const int rc = clip_params("clip_preprocess_color", d, frames, xofs, xcoef, yofs, ycoef, true, &p);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(c && dst, "clip_preprocess_color: NULL buffer");
+  VLFB_REQUIRE(dst_dtype == VLFB_F32 || is16(dst_dtype), "clip_preprocess_color: dst dtype must be f32 or bf16");
+  VLFB_REQUIRE(c->n_ops >= 0 && c->n_ops <= 3, "clip_preprocess_color: n_ops %d is not in 0..3", c->n_ops);
+  ColorP q;
+  bool contrast = false;
+  q.n_ops = c->n_ops;
+  for (int k = 0; k < 3; ++k) {
+    q.op[k] = -1; q.alpha[k] = 1.0f; q.light[k] = c->light[k];
+    if (k >= c->n_ops) continue;
+    VLFB_REQUIRE(c->op[k] >= 0 && c->op[k] <= 2, "clip_preprocess_color: op code %d is not in 0..2", c->op[k]);
+    for (int j = 0; j < k; ++j)
+      VLFB_REQUIRE(c->op[j] != c->op[k], "clip_preprocess_color: op code %d appears twice", c->op[k]);
+    q.op[k] = c->op[k]; q.alpha[k] = c->alpha[k];
+    contrast = contrast || c->op[k] == VLFB_COLOR_CONTRAST;
+  }
+  VLFB_REQUIRE(!contrast || sums, "clip_preprocess_color: a contrast op needs the channel sums");
+  q.sums = contrast ? sums : nullptr;
+  const dim3 grid(grid_for((int64_t)p.crop_h * p.crop_w, 256, 256), p.T);
+  if (dst_dtype == VLFB_F32)
+    hipLaunchKernelGGL(clip_preprocess_color_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p, q, (float*)dst);
+  else
+    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_preprocess_color_kernel<T16>, grid, dim3(256), 0, (hipStream_t)stream, p, q, (T16*)dst));
+  return check_launch("clip_preprocess_color");
+}
 
 extern "C" int vlfb_clip_preprocess(const vlfb_clip_desc* d, const uint8_t* frames, const int32_t* xofs,
                                     const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,

@@ -9,7 +9,13 @@ does resize + crop + flip + /255 + mean/std + BGR->RGB for all frames of the cli
 cfg.MODEL.SAMPLE_THREADS host threads and ships 19.3 MB of fp32 per clip through the blob queue; here
 4.8 MB of uint8 cross PCIe (or nothing, if a GPU decoder produced the frames).
 
-TRAIN.USE_COLOR_AUGMENTATION (off in every shipped config) is not implemented and raises.
+TRAIN.USE_COLOR_AUGMENTATION (off in every shipped config; color_augmentation_list, :142-151, and
+image_processor.py:252-336): `plan_color` draws the order of the brightness / contrast / saturation jitter, their blend
+factors and the PCA lighting offsets from the reference's `np.random` calls, after the geometry as the reference does, and
+two kernels replace `vlfb_clip_preprocess` for that clip: `vlfb_clip_channel_sums` (integer per-frame channel sums of the
+crop window, from which the contrast op's grey mean follows exactly) and `vlfb_clip_preprocess_color` (the same walk with
+the colour chain between /255 and the normalisation).  The sums stay on the device.  The reference reads
+cfg.TRAIN.PCA_JITTER_ONLY, which its config.py never defines; a missing key is read as False here (jitter and lighting).
 """
 import ctypes as C
 import math
@@ -63,8 +69,6 @@ def plan_clip(height, width, split, crop_size, spatial_shift_pos, boxes=None, rn
         boxes[:, [1, 3]] *= height
         boxes = _clip_boxes(boxes, height, width)
     if split == 1:
-        if cfg.TRAIN.USE_COLOR_AUGMENTATION:
-            raise NotImplementedError("TRAIN.USE_COLOR_AUGMENTATION is not available in the device pipeline")
         lo, hi = cfg.TRAIN.JITTER_SCALES
         size = int(round(1.0 / rng.uniform(1.0 / hi, 1.0 / lo)))
         nh, nw = _scaled_size(height, width, size)
@@ -113,6 +117,52 @@ def plan_clip(height, width, split, crop_size, spatial_shift_pos, boxes=None, rn
     return dict(resized_h=nh, resized_w=nw, y0=y0, x0=x0, flip=int(flip)), boxes
 
 
+def plan_color(rng=np.random):
+    """colour augmentation of one train clip: None unless cfg.TRAIN.USE_COLOR_AUGMENTATION, else dict(ops, alphas, light)
+    -- the jitter ops in the order they are applied (0 brightness, 1 contrast, 2 saturation), their blend factors, and
+    the PCA lighting offset per SOURCE channel (B, G, R).  Draws, in the reference's order: permutation + one uniform per
+    op (color_jitter_list, image_processor.py:317-336; skipped with TRAIN.PCA_JITTER_ONLY), then the normal of
+    lighting_list (:253-269)."""
+    if not cfg.TRAIN.USE_COLOR_AUGMENTATION:
+        return None
+    ops, alphas = [], []
+    if not cfg.TRAIN.get("PCA_JITTER_ONLY", False):
+        for k in rng.permutation(np.arange(3)):
+            ops.append(int(k))
+            alphas.append(1.0 + rng.uniform(-0.4, 0.4))
+    alpha = rng.normal(0, 0.1, size=(1, 3))
+    eigval = np.array(cfg.TRAIN.PCA_EIGVAL).astype(np.float32).reshape(1, 3)
+    eigvec = np.array(cfg.TRAIN.PCA_EIGVEC).astype(np.float32)
+    rgb = np.sum(eigvec * np.repeat(alpha, 3, axis=0) * np.repeat(eigval, 3, axis=0), axis=1)
+    return dict(ops=ops, alphas=alphas, light=[float(rgb[2 - c]) for c in range(3)])
+
+
+def clip_desc(plan, frames, height, width, crop_size, w_pad=0, c_pad=3):
+    """the kernels' descriptor of a `plan_clip` plan"""
+    d = hip.ClipDesc()
+    d.frames, d.src_h, d.src_w = frames, height, width
+    d.resized_h, d.resized_w = plan["resized_h"], plan["resized_w"]
+    d.crop_h = d.crop_w = crop_size
+    d.y0, d.x0, d.flip = plan["y0"], plan["x0"], plan["flip"]
+    d.to_rgb = 0 if cfg.MODEL.USE_BGR else 1
+    d.w_left, d.w_total, d.c_pad = w_pad, crop_size + 2 * w_pad, c_pad
+    for c in range(3):
+        d.mean[c] = float(np.float32(cfg.DATA_MEAN[c]))
+        d.std[c] = float(np.float32(cfg.DATA_STD[c]))
+    return d
+
+
+def color_desc(color):
+    """the colour kernel's descriptor of a `plan_color` plan"""
+    q = hip.ClipColorDesc()
+    q.n_ops = len(color["ops"])
+    for i, (op, a) in enumerate(zip(color["ops"], color["alphas"])):
+        q.op[i], q.alpha[i] = op, float(np.float32(a))
+    for c in range(3):
+        q.light[c] = float(np.float32(color["light"][c]))
+    return q
+
+
 _table_cache = {}
 
 
@@ -136,25 +186,23 @@ def images_and_boxes_preprocessing(imgs, split, crop_size, spatial_shift_pos, bo
     frames = imgs.to(device).contiguous()
     T, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     plan, boxes = plan_clip(H, W, split, crop_size, spatial_shift_pos, boxes, rng)
+    color = plan_color(rng) if split == 1 else None        # the reference draws the colours after the pixels are cut
     wtot = crop_size + 2 * w_pad
     if out is None:
         out = torch.zeros(T, crop_size, wtot, c_pad, device=device, dtype=out_dtype)
     assert out.is_contiguous() and out.numel() == T * crop_size * wtot * c_pad, "destination has the wrong size"
-    d = hip.ClipDesc()
-    d.frames, d.src_h, d.src_w = T, H, W
-    d.resized_h, d.resized_w = plan["resized_h"], plan["resized_w"]
-    d.crop_h = d.crop_w = crop_size
-    d.y0, d.x0, d.flip = plan["y0"], plan["x0"], plan["flip"]
-    d.to_rgb = 0 if cfg.MODEL.USE_BGR else 1
-    d.w_left, d.w_total, d.c_pad = w_pad, wtot, c_pad
-    for c in range(3):
-        d.mean[c] = float(np.float32(cfg.DATA_MEAN[c]))
-        d.std[c] = float(np.float32(cfg.DATA_STD[c]))
+    d = clip_desc(plan, T, H, W, crop_size, w_pad, c_pad)
     xo = xc = yo = yc = None
     if (d.resized_h, d.resized_w) != (H, W):
         xo, xc = _tables(W, d.resized_w, frames.device)
         yo, yc = _tables(H, d.resized_h, frames.device)
-    hip.call("vlfb_clip_preprocess", C.byref(d), hip.ptr(frames), hip.ptr(xo), hip.ptr(xc), hip.ptr(yo), hip.ptr(yc),
-             hip.ptr(out), hip.dtype_code(out.dtype))
+    src = (hip.ptr(frames), hip.ptr(xo), hip.ptr(xc), hip.ptr(yo), hip.ptr(yc))
+    if color is None:
+        hip.call("vlfb_clip_preprocess", C.byref(d), *src, hip.ptr(out), hip.dtype_code(out.dtype))
+    else:
+        sums = torch.empty(T, hip.CLIP_SUM_BANDS, 3, device=frames.device, dtype=torch.int64)
+        hip.call("vlfb_clip_channel_sums", C.byref(d), *src, hip.ptr(sums))
+        hip.call("vlfb_clip_preprocess_color", C.byref(d), C.byref(color_desc(color)), *src, hip.ptr(sums), hip.ptr(out),
+                 hip.dtype_code(out.dtype))
     torch.cuda.current_stream().synchronize()     # `frames` may be a temporary
     return out, boxes

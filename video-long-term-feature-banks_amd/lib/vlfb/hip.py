@@ -91,6 +91,14 @@ class ClipDesc(C.Structure):
                [("mean", C.c_float * 3), ("std", C.c_float * 3)]
 
 
+CLIP_SUM_BANDS = 8                                                  # vlfb.h VLFB_CLIP_SUM_BANDS
+COLOR_BRIGHTNESS, COLOR_CONTRAST, COLOR_SATURATION = 0, 1, 2        # vlfb_clip_color.op
+
+
+class ClipColorDesc(C.Structure):
+    _fields_ = [("n_ops", C.c_int32), ("op", C.c_int32 * 3), ("alpha", C.c_float * 3), ("light", C.c_float * 3)]
+
+
 class LfbDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_videos", "n_steps", "capacity", "dim", "dtype", "step_base")]
 
@@ -167,6 +175,9 @@ _SIGS = {
     "vlfb_store_scalars": (C.c_int, [_P, C.c_int, _P, _P]),
     "vlfb_scale_inplace": (C.c_int, [_P, _I64, C.c_float, _P]),
     "vlfb_clip_preprocess": (C.c_int, [C.POINTER(ClipDesc), _P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "vlfb_clip_channel_sums": (C.c_int, [C.POINTER(ClipDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "vlfb_clip_preprocess_color": (C.c_int, [C.POINTER(ClipDesc), C.POINTER(ClipColorDesc), _P, _P, _P, _P, _P, _P, _P,
+                                             C.c_int, _P]),
     "vlfb_lfb_bank_bytes": (_I64, [C.POINTER(LfbDesc)]),
     "vlfb_lfb_append": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, C.c_int, _P, _I64, _P, _P]),
     "vlfb_lfb_sample_window": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, C.c_uint64,
