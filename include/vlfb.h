@@ -642,6 +642,46 @@ int vlfb_clip_preprocess_color(const vlfb_clip_desc* d, const vlfb_clip_color* c
                                const int16_t* ycoef, const int64_t* sums, void* dst, int dst_dtype,
                                vlfb_stream_t stream);
 
+/* The clips of one minibatch in one launch each (lib/datasets/clip_loader.py; the reference assembles a minibatch in
+ * lib/datasets/dataloader.py and the *_data_input.py modules, one worker process per clip).  An item is what the three
+ * entry points above take for one clip, with every pointer as a 64-bit device address:
+ *
+ *   offset  0  frames                       uint8 BGR [geo.frames][geo.src_h][geo.src_w][3]
+ *           8  xofs, xcoef, yofs, ycoef     resize tables; may be 0 when resized == src
+ *          40  dst                          frame 0 of this clip's destination
+ *          48  sums                         int64 [geo.frames][VLFB_CLIP_SUM_BANDS][3]; may be 0 without a contrast op
+ *          56  geo                          vlfb_clip_desc, 80 bytes
+ *         136  color                        vlfb_clip_color, 40 bytes; n_ops = 0 and light = 0: no colour chain
+ *   sizeof = VLFB_CLIP_ITEM_BYTES = 176, no padding.
+ *
+ * Items may differ in every field (frames, source / resized size, crop window, flip, colour plan, destination row).
+ * `items_host` is the array the HOST reads: every item is checked with the conditions of the per-clip entry points (crop
+ * window inside the resized frame, tables present when resizing, destination row, op codes, a contrast op has its sums;
+ * 1 <= n_items <= 65535) and a bad one is rejected with a message before anything is launched; both entry points check
+ * the whole item.  `items_dev` is the same array in DEVICE memory, which the caller uploaded in stream order before the
+ * call: each workgroup reads the record of its clip from there (uniform per workgroup), so the host array may be reused
+ * as soon as the call returns and nothing is passed by value.
+ *
+ * vlfb_clip_batch_channel_sums: vlfb_clip_channel_sums for every item whose `sums` is not 0; grid (band, frame, item).
+ * vlfb_clip_batch_preprocess: per item the arithmetic of vlfb_clip_preprocess_color (which with n_ops = 0 and light = 0 is
+ * vlfb_clip_preprocess's, bit for bit); grid (32 x 8 pixel tiles of the crop, frame, item), workgroups past an item's crop
+ * or frames return.  With c_pad == 4 and a destination aligned to one pixel, a pixel is ONE 8-byte (16-bit dst_dtype) or
+ * 16-byte (fp32) store whose fourth channel is zero (the padding channel is zero by contract); otherwise three scalar
+ * stores as in the per-clip kernels.  W-padding pixels are never written. */
+#define VLFB_CLIP_ITEM_BYTES 176
+typedef struct vlfb_clip_item {
+  uint64_t frames;
+  uint64_t xofs, xcoef, yofs, ycoef;
+  uint64_t dst;
+  uint64_t sums;
+  vlfb_clip_desc  geo;
+  vlfb_clip_color color;
+} vlfb_clip_item;
+int vlfb_clip_batch_channel_sums(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                                 vlfb_stream_t stream);
+int vlfb_clip_batch_preprocess(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                               int dst_dtype, vlfb_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics on the device.  Replace the host meter of lib/utils/metrics.py, which fetches `pred` and
  * `labels` from every GPU every iteration (get_multi_gpu_outputs, :514-540), and tools/evaluate_actions.py.

@@ -12,6 +12,9 @@
 //
 // TRAIN.USE_COLOR_AUGMENTATION adds two kernels beside it: an integer per-frame channel-sum pass (the contrast
 // jitter blends with the frame's grey mean) and the same walk with the colour chain before the normalisation.
+//
+// vlfb_clip_batch_* do the work of the three per-clip entry points for the clips of one minibatch in one launch each
+// (lib/datasets/clip_loader.py): the same device functions, one record per clip read from device memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -90,8 +93,7 @@ struct ColorP {
 // its 32-bit counters cannot wrap; from the wave reduction on the sums are 64-bit.
 constexpr int SUM_THREADS = 256;
 
-__global__ void __launch_bounds__(SUM_THREADS) clip_channel_sums_kernel(ClipP p, int64_t* __restrict__ sums) {
-  const int band = blockIdx.x, t = blockIdx.y;
+__device__ __forceinline__ void band_sums(const ClipP& p, int band, int t, int64_t* __restrict__ sums) {
   const int r0 = (int)((long long)band * p.crop_h / VLFB_CLIP_SUM_BANDS);
   const int r1 = (int)((long long)(band + 1) * p.crop_h / VLFB_CLIP_SUM_BANDS);
   const long long n = (long long)(r1 - r0) * p.crop_w;
@@ -125,13 +127,13 @@ __global__ void __launch_bounds__(SUM_THREADS) clip_channel_sums_kernel(ClipP p,
   }
 }
 
-// The walk of clip_preprocess_kernel with the frame on grid axis y and the colour chain between / 255 and the
-// normalisation.  fp32 throughout, one rounding per operation (-ffp-contract=off), in the order the NumPy code applies them.
-template <typename T>
-__global__ void clip_preprocess_color_kernel(ClipP p, ColorP q, T* __restrict__ dst) {
-  const int t = blockIdx.y;
-  // grey mean of the frame as the contrast op meets it: the exact mean of the un-augmented window, times the alphas of
-  // the brightness ops before it (a saturation blend keeps a pixel's grey value: the three weights add to one)
+__global__ void __launch_bounds__(SUM_THREADS) clip_channel_sums_kernel(ClipP p, int64_t* __restrict__ sums) {
+  band_sums(p, blockIdx.x, blockIdx.y, sums);
+}
+
+// grey mean of frame t as the contrast op meets it: the exact mean of the un-augmented window, times the alphas of the
+// brightness ops before it (a saturation blend keeps a pixel's grey value: the three weights add to one)
+__device__ __forceinline__ float contrast_grey_mean(const ClipP& p, const ColorP& q, int t) {
   float grey_mean = 0.0f;
   if (q.sums) {
     int64_t s[3] = {0, 0, 0};
@@ -142,6 +144,44 @@ __global__ void clip_preprocess_color_kernel(ClipP p, ColorP q, T* __restrict__ 
     for (int k = 0; k < q.n_ops && q.op[k] != VLFB_COLOR_CONTRAST; ++k)
       if (q.op[k] == VLFB_COLOR_BRIGHTNESS) grey_mean = grey_mean * q.alpha[k];
   }
+  return grey_mean;
+}
+
+// One pixel from the uint8 values of the resized frame to the normalised values in the SOURCE channel order: / 255, the
+// jitter ops, the lighting offset, (v - mean) / std.  fp32 throughout, one rounding per operation (-ffp-contract=off), in
+// the order the NumPy code applies them.
+__device__ __forceinline__ void color_pixel(const ClipP& p, const ColorP& q, float grey_mean, const uint8_t* frame, int ys,
+                                            int xs, float (&w)[3]) {
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = (float)resized_u8(p, frame, ys, xs, c) / 255.0f;
+  for (int k = 0; k < q.n_ops; ++k) {
+    const float a = q.alpha[k];
+    if (q.op[k] == VLFB_COLOR_BRIGHTNESS) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = v[c] * a;
+    } else {
+      float other = grey_mean;
+      if (q.op[k] == VLFB_COLOR_SATURATION) other = 0.299f * v[2] + 0.587f * v[1] + 0.114f * v[0];
+      const float rest = other * (1.0f - a);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = v[c] * a + rest;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    w[c] = v[c] + q.light[c];
+    w[c] = w[c] - p.mean[c];
+    w[c] = w[c] / p.stdv[c];
+  }
+}
+
+// The walk of clip_preprocess_kernel with the frame on grid axis y and the colour chain between / 255 and the
+// normalisation.
+template <typename T>
+__global__ void clip_preprocess_color_kernel(ClipP p, ColorP q, T* __restrict__ dst) {
+  const int t = blockIdx.y;
+  const float grey_mean = contrast_grey_mean(p, q, t);
   const uint8_t* frame = p.src + (long long)t * p.Hs * p.Ws * 3;
   const long long total = (long long)p.crop_h * p.crop_w;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -150,33 +190,37 @@ __global__ void clip_preprocess_color_kernel(ClipP p, ColorP q, T* __restrict__ 
     const int xs = p.flip ? p.x0 - x : p.x0 + x;
     const int ys = p.y0 + y;
     T* d = dst + ((long long)(t * p.crop_h + y) * p.wtot + p.wl + x) * p.c_pad;
-    float v[3];
+    float w[3];
+    color_pixel(p, q, grey_mean, frame, ys, xs, w);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = (float)resized_u8(p, frame, ys, xs, c) / 255.0f;
-    for (int k = 0; k < q.n_ops; ++k) {
-      const float a = q.alpha[k];
-      if (q.op[k] == VLFB_COLOR_BRIGHTNESS) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = v[c] * a;
-      } else {
-        float other = grey_mean;
-        if (q.op[k] == VLFB_COLOR_SATURATION) other = 0.299f * v[2] + 0.587f * v[1] + 0.114f * v[0];
-        const float rest = other * (1.0f - a);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = v[c] * a + rest;
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float w = v[c] + q.light[c];
-      w = w - p.mean[c];
-      w = w / p.stdv[c];
-      Elem<T>::st(d + (p.to_rgb ? 2 - c : c), w);
-    }
+    for (int c = 0; c < 3; ++c) Elem<T>::st(d + (p.to_rgb ? 2 - c : c), w[c]);
   }
 }
 
-// argument checks and kernel parameters shared by the two colour entry points (`with_dst`: the destination row too)
+// kernel parameters of a descriptor: on the host for the per-clip launches, on the device from a vlfb_clip_item
+__host__ __device__ inline void fill_clip(ClipP* p, const vlfb_clip_desc& d, const uint8_t* frames, const int32_t* xofs,
+                                          const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef) {
+  p->src = frames; p->xofs = xofs; p->xcoef = xcoef; p->yofs = yofs; p->ycoef = ycoef;
+  p->T = d.frames; p->Hs = d.src_h; p->Ws = d.src_w; p->Hr = d.resized_h; p->Wr = d.resized_w;
+  p->resize = (d.resized_h != d.src_h || d.resized_w != d.src_w) ? 1 : 0;
+  p->crop_h = d.crop_h; p->crop_w = d.crop_w; p->y0 = d.y0; p->x0 = d.x0; p->flip = d.flip;
+  for (int c = 0; c < 3; ++c) { p->mean[c] = d.mean[c]; p->stdv[c] = d.std[c]; }
+  p->to_rgb = d.to_rgb; p->wl = d.w_left; p->wtot = d.w_total; p->c_pad = d.c_pad;
+}
+
+__host__ __device__ inline void fill_color(ColorP* q, const vlfb_clip_color& c, const int64_t* sums) {
+  bool contrast = false;
+  q->n_ops = c.n_ops;
+  for (int k = 0; k < 3; ++k) {
+    q->op[k] = -1; q->alpha[k] = 1.0f; q->light[k] = c.light[k];
+    if (k >= c.n_ops) continue;
+    q->op[k] = c.op[k]; q->alpha[k] = c.alpha[k];
+    contrast = contrast || c.op[k] == VLFB_COLOR_CONTRAST;
+  }
+  q->sums = contrast ? sums : nullptr;
+}
+
+// argument checks and kernel parameters shared by the colour and batch entry points (`with_dst`: the destination row too)
 int clip_params(const char* what, const vlfb_clip_desc* d, const uint8_t* frames, const int32_t* xofs, const int16_t* xcoef,
                 const int32_t* yofs, const int16_t* ycoef, bool with_dst, ClipP* p) {
   VLFB_REQUIRE(d && frames, "%s: NULL buffer", what);
@@ -191,12 +235,100 @@ int clip_params(const char* what, const vlfb_clip_desc* d, const uint8_t* frames
   VLFB_REQUIRE((long long)d->crop_h * d->crop_w <= (1ll << 31) - 1, "%s: crop window of more than 2^31 - 1 pixels", what);
   if (with_dst)
     VLFB_REQUIRE(d->c_pad >= 3 && d->w_left >= 0 && d->w_total >= d->w_left + d->crop_w, "%s: bad destination row", what);
-  p->src = frames; p->xofs = xofs; p->xcoef = xcoef; p->yofs = yofs; p->ycoef = ycoef;
-  p->T = d->frames; p->Hs = d->src_h; p->Ws = d->src_w; p->Hr = d->resized_h; p->Wr = d->resized_w;
-  p->resize = resize ? 1 : 0;
-  p->crop_h = d->crop_h; p->crop_w = d->crop_w; p->y0 = d->y0; p->x0 = d->x0; p->flip = d->flip;
-  for (int c = 0; c < 3; ++c) { p->mean[c] = d->mean[c]; p->stdv[c] = d->std[c]; }
-  p->to_rgb = d->to_rgb; p->wl = d->w_left; p->wtot = d->w_total; p->c_pad = d->c_pad;
+  fill_clip(p, *d, frames, xofs, xcoef, yofs, ycoef);
+  return VLFB_OK;
+}
+
+int color_params(const char* what, const vlfb_clip_color* c, const int64_t* sums, ColorP* q) {
+  VLFB_REQUIRE(c->n_ops >= 0 && c->n_ops <= 3, "%s: n_ops %d is not in 0..3", what, c->n_ops);
+  bool contrast = false;
+  for (int k = 0; k < c->n_ops; ++k) {
+    VLFB_REQUIRE(c->op[k] >= 0 && c->op[k] <= 2, "%s: op code %d is not in 0..2", what, c->op[k]);
+    for (int j = 0; j < k; ++j)
+      VLFB_REQUIRE(c->op[j] != c->op[k], "%s: op code %d appears twice", what, c->op[k]);
+    contrast = contrast || c->op[k] == VLFB_COLOR_CONTRAST;
+  }
+  VLFB_REQUIRE(!contrast || sums, "%s: a contrast op needs the channel sums", what);
+  fill_color(q, *c, sums);
+  return VLFB_OK;
+}
+
+// ---- the clips of one minibatch in one launch (vlfb_clip_item, include/vlfb.h) ----
+// The record of a workgroup's clip comes from device memory at an address that depends on blockIdx.z only: const and
+// __restrict__, so the loads are scalar loads and the geometry lives in SGPRs, as the by-value ClipP of the per-clip kernels.
+static_assert(sizeof(vlfb_clip_item) == VLFB_CLIP_ITEM_BYTES, "vlfb_clip_item layout (include/vlfb.h, vlfb/hip.py ClipItem)");
+constexpr int TILE_W = 32, TILE_H = 8;     // 224 = 7 * 32: no idle lanes at the shipped crop; a wave stores 2 rows of 32 pixels
+
+__device__ __forceinline__ void item_params(const vlfb_clip_item& it, ClipP* p, ColorP* q) {
+  fill_clip(p, it.geo, (const uint8_t*)it.frames, (const int32_t*)it.xofs, (const int16_t*)it.xcoef, (const int32_t*)it.yofs,
+            (const int16_t*)it.ycoef);
+  fill_color(q, it.color, (const int64_t*)it.sums);
+}
+
+__global__ void __launch_bounds__(SUM_THREADS) clip_batch_channel_sums_kernel(const vlfb_clip_item* __restrict__ items) {
+  const vlfb_clip_item& it = items[blockIdx.z];
+  const int t = blockIdx.y;
+  if (!it.sums || t >= it.geo.frames) return;
+  ClipP p;
+  ColorP q;
+  item_params(it, &p, &q);
+  band_sums(p, blockIdx.x, t, (int64_t*)it.sums);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TILE_W * TILE_H) clip_batch_preprocess_kernel(const vlfb_clip_item* __restrict__ items) {
+  const vlfb_clip_item& it = items[blockIdx.z];
+  const int t = blockIdx.y;
+  const int tiles_x = (it.geo.crop_w + TILE_W - 1) / TILE_W;             // (uniform: one 32-bit division per workgroup)
+  const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+  if (t >= it.geo.frames || ty * TILE_H >= it.geo.crop_h) return;
+  const int x = tx * TILE_W + (int)threadIdx.x, y = ty * TILE_H + (int)threadIdx.y;
+  ClipP p;
+  ColorP q;
+  item_params(it, &p, &q);
+  if (x >= p.crop_w || y >= p.crop_h) return;
+  const float grey_mean = contrast_grey_mean(p, q, t);
+  const int xs = p.flip ? p.x0 - x : p.x0 + x;
+  const int ys = p.y0 + y;
+  const uint8_t* frame = p.src + (long long)t * p.Hs * p.Ws * 3;
+  T* d = (T*)it.dst + ((long long)(t * p.crop_h + y) * p.wtot + p.wl + x) * p.c_pad;
+  float w[3];
+  color_pixel(p, q, grey_mean, frame, ys, xs, w);
+  const float o0 = p.to_rgb ? w[2] : w[0], o2 = p.to_rgb ? w[0] : w[2];
+  if (p.c_pad == 4 && it.dst % (4 * sizeof(T)) == 0) {                   // one store per pixel; the padding channel is zero
+    if constexpr (sizeof(T) == 4)
+      *reinterpret_cast<float4*>(d) = make_float4(o0, w[1], o2, 0.0f);
+    else
+      *reinterpret_cast<uint2*>(d) = make_uint2(Elem<T>::pack2(o0, w[1]), Elem<T>::pack2(o2, 0.0f));
+  } else {
+    Elem<T>::st(d, o0);
+    Elem<T>::st(d + 1, w[1]);
+    Elem<T>::st(d + 2, o2);
+  }
+}
+
+// every item of the host array against the conditions of the per-clip entry points; the grid extents over the items
+int check_items(const char* what, const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                int* max_frames, int* max_tiles, bool* any_sums) {
+  VLFB_REQUIRE(items_host && items_dev, "%s: NULL item array", what);
+  VLFB_REQUIRE(n_items >= 1 && n_items <= 65535, "%s: n_items %d is not in 1..65535", what, n_items);
+  *max_frames = 0; *max_tiles = 0; *any_sums = false;
+  for (int i = 0; i < n_items; ++i) {
+    const vlfb_clip_item& it = items_host[i];
+    ClipP p;
+    ColorP q;
+    int rc = clip_params(what, &it.geo, (const uint8_t*)it.frames, (const int32_t*)it.xofs, (const int16_t*)it.xcoef,
+                         (const int32_t*)it.yofs, (const int16_t*)it.ycoef, true, &p);
+    if (rc != VLFB_OK) return rc;
+    VLFB_REQUIRE(it.dst, "%s: NULL buffer", what);
+    rc = color_params(what, &it.color, (const int64_t*)it.sums, &q);
+    if (rc != VLFB_OK) return rc;
+    const long long tiles = (long long)((p.crop_w + TILE_W - 1) / TILE_W) * ((p.crop_h + TILE_H - 1) / TILE_H);
+    VLFB_REQUIRE(tiles <= 0x7fffffffll, "%s: crop window of more than 2^31 - 1 tiles", what);
+    if (p.T > *max_frames) *max_frames = p.T;
+    if ((int)tiles > *max_tiles) *max_tiles = (int)tiles;
+    *any_sums = *any_sums || it.sums != 0;
+  }
   return VLFB_OK;
 }
 
@@ -225,21 +357,9 @@ extern "C" int vlfb_clip_preprocess_color(const vlfb_clip_desc* d, const vlfb_cl
   if (rc != VLFB_OK) return rc;
   VLFB_REQUIRE(c && dst, "clip_preprocess_color: NULL buffer");
   VLFB_REQUIRE(dst_dtype == VLFB_F32 || is16(dst_dtype), "clip_preprocess_color: dst dtype must be f32 or bf16");
-  VLFB_REQUIRE(c->n_ops >= 0 && c->n_ops <= 3, "clip_preprocess_color: n_ops %d is not in 0..3", c->n_ops);
   ColorP q;
-  bool contrast = false;
-  q.n_ops = c->n_ops;
-  for (int k = 0; k < 3; ++k) {
-    q.op[k] = -1; q.alpha[k] = 1.0f; q.light[k] = c->light[k];
-    if (k >= c->n_ops) continue;
-    VLFB_REQUIRE(c->op[k] >= 0 && c->op[k] <= 2, "clip_preprocess_color: op code %d is not in 0..2", c->op[k]);
-    for (int j = 0; j < k; ++j)
-      VLFB_REQUIRE(c->op[j] != c->op[k], "clip_preprocess_color: op code %d appears twice", c->op[k]);
-    q.op[k] = c->op[k]; q.alpha[k] = c->alpha[k];
-    contrast = contrast || c->op[k] == VLFB_COLOR_CONTRAST;
-  }
-  VLFB_REQUIRE(!contrast || sums, "clip_preprocess_color: a contrast op needs the channel sums");
-  q.sums = contrast ? sums : nullptr;
+  const int rq = color_params("clip_preprocess_color", c, sums, &q);
+  if (rq != VLFB_OK) return rq;
   const dim3 grid(grid_for((int64_t)p.crop_h * p.crop_w, 256, 256), p.T);
   if (dst_dtype == VLFB_F32)
     hipLaunchKernelGGL(clip_preprocess_color_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p, q, (float*)dst);
@@ -274,4 +394,31 @@ extern "C" int vlfb_clip_preprocess(const vlfb_clip_desc* d, const uint8_t* fram
   else
     VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_preprocess_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, (T16*)dst));
   return check_launch("clip_preprocess");
+}
+
+extern "C" int vlfb_clip_batch_channel_sums(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                                            vlfb_stream_t stream) {
+  int frames, tiles;
+  bool any_sums;
+  const int rc = check_items("clip_batch_channel_sums", items_host, items_dev, n_items, &frames, &tiles, &any_sums);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(any_sums, "clip_batch_channel_sums: no item has a sums buffer");
+  hipLaunchKernelGGL(clip_batch_channel_sums_kernel, dim3(VLFB_CLIP_SUM_BANDS, frames, n_items), dim3(SUM_THREADS), 0,
+                     (hipStream_t)stream, items_dev);
+  return check_launch("clip_batch_channel_sums");
+}
+
+extern "C" int vlfb_clip_batch_preprocess(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                                          int dst_dtype, vlfb_stream_t stream) {
+  int frames, tiles;
+  bool any_sums;
+  const int rc = check_items("clip_batch_preprocess", items_host, items_dev, n_items, &frames, &tiles, &any_sums);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(dst_dtype == VLFB_F32 || is16(dst_dtype), "clip_batch_preprocess: dst dtype must be f32 or bf16");
+  const dim3 grid(tiles, frames, n_items), block(TILE_W, TILE_H);
+  if (dst_dtype == VLFB_F32)
+    hipLaunchKernelGGL(clip_batch_preprocess_kernel<float>, grid, block, 0, (hipStream_t)stream, items_dev);
+  else
+    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_batch_preprocess_kernel<T16>, grid, block, 0, (hipStream_t)stream, items_dev));
+  return check_launch("clip_batch_preprocess");
 }

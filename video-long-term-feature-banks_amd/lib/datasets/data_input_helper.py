@@ -19,6 +19,7 @@ cfg.TRAIN.PCA_JITTER_ONLY, which its config.py never defines; a missing key is r
 """
 import ctypes as C
 import math
+import threading
 
 import numpy as np
 import torch
@@ -164,14 +165,16 @@ def color_desc(color):
 
 
 _table_cache = {}
+_table_lock = threading.Lock()        # the training thread and a loader thread (datasets.clip_loader) share the cache
 
 
 def _tables(src, dst, device):
     key = (src, dst, str(device))
-    if key not in _table_cache:
-        ofs, coef = resize_tables(src, dst)
-        _table_cache[key] = (torch.as_tensor(ofs).to(device), torch.as_tensor(coef).to(device))
-    return _table_cache[key]
+    with _table_lock:
+        if key not in _table_cache:
+            ofs, coef = resize_tables(src, dst)
+            _table_cache[key] = (torch.as_tensor(ofs).to(device), torch.as_tensor(coef).to(device))
+        return _table_cache[key]
 
 
 def images_and_boxes_preprocessing(imgs, split, crop_size, spatial_shift_pos, boxes=None, out=None,
@@ -206,3 +209,82 @@ def images_and_boxes_preprocessing(imgs, split, crop_size, spatial_shift_pos, bo
                  hip.dtype_code(out.dtype))
     torch.cuda.current_stream().synchronize()     # `frames` may be a temporary
     return out, boxes
+
+
+# ---- the clips of one minibatch on one plan (datasets.clip_loader; vlfb.h vlfb_clip_item) ----
+
+def plan_minibatch(sizes, split, crop_size, spatial_shift_pos, boxes_list=None, rng=np.random):
+    """geometry and colour plans of the clips of one minibatch: `sizes` are the (height, width) of the clips' frames,
+    `boxes_list` the clips' normalised boxes (or None, or None entries), `spatial_shift_pos` one position or one per clip.
+    Returns (plans, colors, boxes): per clip what `plan_clip` and `plan_color` return.
+
+    All draws come from the ONE `rng`, in minibatch order: clip 0's geometry, clip 0's colour, clip 1's geometry, ... --
+    exactly what len(sizes) successive calls of `images_and_boxes_preprocessing` with that `rng` draw.  The reference
+    preprocesses each clip in a worker process with a random state of its own (ava_data_input.py:117-128) and defines no
+    order across the clips of a minibatch; this order is the definition here."""
+    n = len(sizes)
+    if boxes_list is None:
+        boxes_list = [None] * n
+    shifts = list(spatial_shift_pos) if isinstance(spatial_shift_pos, (list, tuple, np.ndarray)) else [spatial_shift_pos] * n
+    assert len(boxes_list) == n and len(shifts) == n, "plan_minibatch: one entry per clip"
+    plans, colors, boxes = [], [], []
+    for (h, w), shift, b in zip(sizes, shifts, boxes_list):
+        plan, b = plan_clip(int(h), int(w), split, crop_size, shift, b, rng)
+        plans.append(plan)
+        colors.append(plan_color(rng) if split == 1 else None)
+        boxes.append(b)
+    return plans, colors, boxes
+
+
+def warm_tables(sizes, split, device):
+    """build the resize tables every plan of sources of these (height, width) can ask for (all TRAIN.JITTER_SCALES of a
+    train split, TEST.SCALE otherwise), so that a loader thread finds them in the cache and allocates nothing"""
+    lo, hi = (cfg.TRAIN.JITTER_SCALES if split == 1 else (cfg.TEST.SCALE, cfg.TEST.SCALE))
+    for h, w in sizes:
+        for size in range(int(lo), int(hi) + 1):
+            nh, nw = _scaled_size(int(h), int(w), size)
+            if (nh, nw) != (int(h), int(w)):
+                _tables(int(w), nw, device)
+                _tables(int(h), nh, device)
+
+
+def pack_items(items, plans, colors, frames, sizes, crop_size, frame_ptrs, dst_ptrs, sums_ptrs, w_pad, c_pad, device):
+    """fill `items` (a ctypes array of hip.ClipItem, e.g. over a pinned buffer) for the vlfb_clip_batch_* entry points:
+    clip i has frames[i] frames of sizes[i] = (height, width) at device address frame_ptrs[i], goes to dst_ptrs[i] and,
+    if its colour plan has a contrast op, sums to sums_ptrs[i].  Table pointers come from the `_tables` cache.  Returns
+    True when some item needs the sums launch."""
+    need_sums = False
+    for i, (plan, color) in enumerate(zip(plans, colors)):
+        it = items[i]
+        h, w = int(sizes[i][0]), int(sizes[i][1])
+        it.geo = clip_desc(plan, int(frames[i]), h, w, crop_size, w_pad, c_pad)
+        it.frames, it.dst = int(frame_ptrs[i]), int(dst_ptrs[i])
+        it.xofs = it.xcoef = it.yofs = it.ycoef = 0
+        if (plan["resized_h"], plan["resized_w"]) != (h, w):
+            xo, xc = _tables(w, plan["resized_w"], device)
+            yo, yc = _tables(h, plan["resized_h"], device)
+            it.xofs, it.xcoef, it.yofs, it.ycoef = xo.data_ptr(), xc.data_ptr(), yo.data_ptr(), yc.data_ptr()
+        it.color = color_desc(color) if color is not None else hip.ClipColorDesc()
+        contrast = color is not None and hip.COLOR_CONTRAST in color["ops"]
+        it.sums = int(sums_ptrs[i]) if contrast else 0
+        need_sums = need_sums or contrast
+    return need_sums
+
+
+def minibatch_rows(boxes, labels_list, rows, num_classes):
+    """the RoI rows of a minibatch as the model's inputs take them: proposals (rows, 5) fp32 = [clip index, x1, y1, x2,
+    y2] per box in clip order (ava_data_input.py:175-192) and labels (rows, num_classes) int32, padded to the planned
+    `rows` as Engine.feed pads a ragged batch: labels -1, box 0 of clip 0.  Returns (proposals, labels, used rows)."""
+    props = np.zeros((rows, 5), dtype=np.float32)
+    labels = np.full((rows, num_classes), -1, dtype=np.int32)
+    r = 0
+    for n, b in enumerate(boxes):
+        k = 0 if b is None else len(b)
+        if k == 0:
+            continue
+        assert r + k <= rows, "minibatch of more than the planned %d RoI rows" % rows
+        props[r:r + k, 0] = n
+        props[r:r + k, 1:] = np.asarray(b)[:, :4]
+        labels[r:r + k] = np.asarray(labels_list[n], dtype=np.int32).reshape(k, num_classes)
+        r += k
+    return props, labels, r

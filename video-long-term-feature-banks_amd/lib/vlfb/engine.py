@@ -2789,6 +2789,17 @@ class Engine(object):
         n = N * T * H * (W + 2 * wpad) * b.pad_c
         return b.tensor[:n].view(N, T, H, W + 2 * wpad, b.pad_c), (wpad, b.pad_c)
 
+    def input_tensor(self, name):
+        """the flat storage tensor of an INPUT blob as planned (labels int32 (R * classes), proposals fp32 (R * 5), lfb in
+        the engine's dtype (R * K * D), data padded as blob_padded describes), for a device-side feeder that copies a whole
+        blob in stream order between steps (datasets.clip_loader.MinibatchLoader.deliver).  Anything else is refused."""
+        b = self.env[name] if name in self.env else None
+        if b is None or not getattr(b.root, "is_input", False) and not getattr(b, "is_input", False):
+            raise KeyError("%r is not an input blob of this model" % name)
+        if b.root.pair:
+            raise KeyError("input blob %r is stored as two planes; use feed()" % name)
+        return b.root.tensor
+
     def fetch(self, name):
         """blob (or its gradient with suffix '_grad') as a float32 numpy array in the reference layout"""
         grad = False

@@ -99,6 +99,16 @@ class ClipColorDesc(C.Structure):
     _fields_ = [("n_ops", C.c_int32), ("op", C.c_int32 * 3), ("alpha", C.c_float * 3), ("light", C.c_float * 3)]
 
 
+class ClipItem(C.Structure):
+    """vlfb.h vlfb_clip_item: one clip of a minibatch for the vlfb_clip_batch_* entry points; pointers are device addresses"""
+    _fields_ = [(n, C.c_uint64) for n in ("frames", "xofs", "xcoef", "yofs", "ycoef", "dst", "sums")] + \
+               [("geo", ClipDesc), ("color", ClipColorDesc)]
+
+
+CLIP_ITEM_BYTES = 176                                               # vlfb.h VLFB_CLIP_ITEM_BYTES
+assert C.sizeof(ClipItem) == CLIP_ITEM_BYTES
+
+
 class LfbDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_videos", "n_steps", "capacity", "dim", "dtype", "step_base")]
 
@@ -178,6 +188,8 @@ _SIGS = {
     "vlfb_clip_channel_sums": (C.c_int, [C.POINTER(ClipDesc), _P, _P, _P, _P, _P, _P, _P]),
     "vlfb_clip_preprocess_color": (C.c_int, [C.POINTER(ClipDesc), C.POINTER(ClipColorDesc), _P, _P, _P, _P, _P, _P, _P,
                                              C.c_int, _P]),
+    "vlfb_clip_batch_channel_sums": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vlfb_clip_batch_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "vlfb_lfb_bank_bytes": (_I64, [C.POINTER(LfbDesc)]),
     "vlfb_lfb_append": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, C.c_int, _P, _I64, _P, _P]),
     "vlfb_lfb_sample_window": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, C.c_uint64,

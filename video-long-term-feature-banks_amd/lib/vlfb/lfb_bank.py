@@ -205,6 +205,19 @@ class DeviceBank(object):
         torch.cuda.current_stream().synchronize()
         return out
 
+    def window_query(self, videos, secs, sample_ids):
+        """the (rows, 3) int32 query `sample_window` uploads: [bank row of the video, step, sample id]"""
+        return np.stack([self._rows_of(videos), np.asarray(secs).astype(np.int64).reshape(-1) - self.step_base,
+                         np.asarray(sample_ids).astype(np.int64).reshape(-1) & 0x7FFFFFFF], axis=1).astype(np.int32)
+
+    def sample_window_enqueue(self, query_dev, rows, window, max_per_step, seed, out):
+        """`sample_window` for a caller that owns every buffer (a `window_query` it uploaded to `query_dev` in stream order,
+        the output rows): one launch on the current stream, nothing allocated, no synchronisation"""
+        assert out.is_contiguous() and out.numel() >= int(rows) * int(window) * int(max_per_step) * self.dim
+        hip.call("vlfb_lfb_sample_window", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(query_dev),
+                 int(rows), int(window), int(max_per_step), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), hip.ptr(out),
+                 hip.dtype_code(out.dtype))
+
     def sample_window_reference_draw(self, videos, secs, clip_index, window, max_per_step, rng=None, out=None, out_dtype=None):
         """AVA (ava.py:300-323) with the reference's OWN random stream: the host makes exactly the calls `sample_lfb` makes
         (reference_draw_table below) and the device gathers (vlfb_lfb_gather_slots).  `clip_index[r]` = the position of row r's
