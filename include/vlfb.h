@@ -682,6 +682,27 @@ int vlfb_clip_batch_channel_sums(const vlfb_clip_item* items_host, const vlfb_cl
 int vlfb_clip_batch_preprocess(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
                                int dst_dtype, vlfb_stream_t stream);
 
+/* The same two launches for clips given as frame lists into a frame store (lib/datasets/frame_store.py; the reference's
+ * clips are index lists, dataset_helper.get_sequence, and the clips of a bank-construction pass share most frames):
+ * `items[i].frames` points at a store uint8 BGR [store_frames_host[i]][geo.src_h][geo.src_w][3], and destination frame t
+ * of item i reads source frame index[i * index_stride + t] of it.  Entries may repeat (a sequence clamped at a video's
+ * ends) and come in any order; items may share a store or name different ones.  Everything else -- the item record, the
+ * arithmetic, the grids, the stores, `sums` indexed by the DESTINATION frame t -- is that of the two entry points above
+ * (the same device functions; with index[t] = t the output is theirs bit for bit).
+ *
+ * `index_host` is the table the HOST reads, `index_dev` the same int32 table in DEVICE memory, uploaded by the caller in
+ * stream order as `items_dev` is; a workgroup reads its one entry from there (uniform per workgroup), nothing is passed
+ * by value.  `store_frames_host` [n_items] is read by the host only.  Checked before anything is launched, beside the
+ * conditions on the items: index_stride >= geo.frames, store_frames_host[i] >= 1, and 0 <= index < store_frames_host[i]
+ * for the first geo.frames entries of every item (entries past geo.frames are not read); a bad table is rejected with
+ * VLFB_ERR_ARG and a message that names the item and the entry. */
+int vlfb_clip_batch_channel_sums_indexed(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                                         const int32_t* index_host, const int32_t* index_dev, int index_stride,
+                                         const int32_t* store_frames_host, vlfb_stream_t stream);
+int vlfb_clip_batch_preprocess_indexed(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                                       const int32_t* index_host, const int32_t* index_dev, int index_stride,
+                                       const int32_t* store_frames_host, int dst_dtype, vlfb_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics on the device.  Replace the host meter of lib/utils/metrics.py, which fetches `pred` and
  * `labels` from every GPU every iteration (get_multi_gpu_outputs, :514-540), and tools/evaluate_actions.py.

@@ -93,11 +93,12 @@ struct ColorP {
 // its 32-bit counters cannot wrap; from the wave reduction on the sums are 64-bit.
 constexpr int SUM_THREADS = 256;
 
-__device__ __forceinline__ void band_sums(const ClipP& p, int band, int t, int64_t* __restrict__ sums) {
+// (`f` is the frame of p.src that destination frame t reads: t itself but for the _indexed entry points)
+__device__ __forceinline__ void band_sums(const ClipP& p, int band, int t, int f, int64_t* __restrict__ sums) {
   const int r0 = (int)((long long)band * p.crop_h / VLFB_CLIP_SUM_BANDS);
   const int r1 = (int)((long long)(band + 1) * p.crop_h / VLFB_CLIP_SUM_BANDS);
   const long long n = (long long)(r1 - r0) * p.crop_w;
-  const uint8_t* frame = p.src + (long long)t * p.Hs * p.Ws * 3;
+  const uint8_t* frame = p.src + (long long)f * p.Hs * p.Ws * 3;
   uint32_t acc[3] = {0u, 0u, 0u};
   for (long long i = threadIdx.x; i < n; i += SUM_THREADS) {
     const int x = (int)(i % p.crop_w);
@@ -128,7 +129,7 @@ __device__ __forceinline__ void band_sums(const ClipP& p, int band, int t, int64
 }
 
 __global__ void __launch_bounds__(SUM_THREADS) clip_channel_sums_kernel(ClipP p, int64_t* __restrict__ sums) {
-  band_sums(p, blockIdx.x, blockIdx.y, sums);
+  band_sums(p, blockIdx.x, blockIdx.y, blockIdx.y, sums);
 }
 
 // grey mean of frame t as the contrast op meets it: the exact mean of the un-augmented window, times the alphas of the
@@ -265,18 +266,36 @@ __device__ __forceinline__ void item_params(const vlfb_clip_item& it, ClipP* p, 
   fill_color(q, it.color, (const int64_t*)it.sums);
 }
 
-__global__ void __launch_bounds__(SUM_THREADS) clip_batch_channel_sums_kernel(const vlfb_clip_item* __restrict__ items) {
+// The _indexed entry points read source frame index[item * index_stride + t] of the frame store `frames` points at.  The
+// entry depends on blockIdx only (a uniform load, as the item record); `index` is NULL for the contiguous entry points,
+// a constant after inlining, so their kernels are the ones they were.
+__device__ __forceinline__ int source_frame(const int32_t* __restrict__ index, int index_stride, int t) {
+  return index ? index[(long long)blockIdx.z * index_stride + t] : t;
+}
+
+__device__ __forceinline__ void batch_channel_sums(const vlfb_clip_item* __restrict__ items, const int32_t* __restrict__ index,
+                                                   int index_stride) {
   const vlfb_clip_item& it = items[blockIdx.z];
   const int t = blockIdx.y;
   if (!it.sums || t >= it.geo.frames) return;
   ClipP p;
   ColorP q;
   item_params(it, &p, &q);
-  band_sums(p, blockIdx.x, t, (int64_t*)it.sums);
+  band_sums(p, blockIdx.x, t, source_frame(index, index_stride, t), (int64_t*)it.sums);
+}
+
+__global__ void __launch_bounds__(SUM_THREADS) clip_batch_channel_sums_kernel(const vlfb_clip_item* __restrict__ items) {
+  batch_channel_sums(items, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(SUM_THREADS) clip_batch_channel_sums_indexed_kernel(
+    const vlfb_clip_item* __restrict__ items, const int32_t* __restrict__ index, int index_stride) {
+  batch_channel_sums(items, index, index_stride);
 }
 
 template <typename T>
-__global__ void __launch_bounds__(TILE_W * TILE_H) clip_batch_preprocess_kernel(const vlfb_clip_item* __restrict__ items) {
+__device__ __forceinline__ void batch_preprocess(const vlfb_clip_item* __restrict__ items, const int32_t* __restrict__ index,
+                                                 int index_stride) {
   const vlfb_clip_item& it = items[blockIdx.z];
   const int t = blockIdx.y;
   const int tiles_x = (it.geo.crop_w + TILE_W - 1) / TILE_W;             // (uniform: one 32-bit division per workgroup)
@@ -290,7 +309,7 @@ __global__ void __launch_bounds__(TILE_W * TILE_H) clip_batch_preprocess_kernel(
   const float grey_mean = contrast_grey_mean(p, q, t);
   const int xs = p.flip ? p.x0 - x : p.x0 + x;
   const int ys = p.y0 + y;
-  const uint8_t* frame = p.src + (long long)t * p.Hs * p.Ws * 3;
+  const uint8_t* frame = p.src + (long long)source_frame(index, index_stride, t) * p.Hs * p.Ws * 3;
   T* d = (T*)it.dst + ((long long)(t * p.crop_h + y) * p.wtot + p.wl + x) * p.c_pad;
   float w[3];
   color_pixel(p, q, grey_mean, frame, ys, xs, w);
@@ -305,6 +324,17 @@ __global__ void __launch_bounds__(TILE_W * TILE_H) clip_batch_preprocess_kernel(
     Elem<T>::st(d + 1, w[1]);
     Elem<T>::st(d + 2, o2);
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TILE_W * TILE_H) clip_batch_preprocess_kernel(const vlfb_clip_item* __restrict__ items) {
+  batch_preprocess<T>(items, nullptr, 0);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TILE_W * TILE_H) clip_batch_preprocess_indexed_kernel(
+    const vlfb_clip_item* __restrict__ items, const int32_t* __restrict__ index, int index_stride) {
+  batch_preprocess<T>(items, index, index_stride);
 }
 
 // every item of the host array against the conditions of the per-clip entry points; the grid extents over the items
@@ -328,6 +358,24 @@ int check_items(const char* what, const vlfb_clip_item* items_host, const vlfb_c
     if (p.T > *max_frames) *max_frames = p.T;
     if ((int)tiles > *max_tiles) *max_tiles = (int)tiles;
     *any_sums = *any_sums || it.sums != 0;
+  }
+  return VLFB_OK;
+}
+
+// the frame table of the _indexed entry points: item i reads index_host[i * index_stride + t], t < geo.frames, of a store of
+// store_frames_host[i] frames
+int check_index(const char* what, const vlfb_clip_item* items_host, int n_items, const int32_t* index_host,
+                const int32_t* index_dev, int index_stride, const int32_t* store_frames_host) {
+  VLFB_REQUIRE(index_host && index_dev && store_frames_host, "%s: NULL frame table", what);
+  for (int i = 0; i < n_items; ++i) {
+    const int frames = items_host[i].geo.frames;
+    VLFB_REQUIRE(index_stride >= frames, "%s: item %d has %d frames, index_stride is %d", what, i, frames, index_stride);
+    VLFB_REQUIRE(store_frames_host[i] >= 1, "%s: item %d reads a store of %d frames", what, i, store_frames_host[i]);
+    for (int t = 0; t < frames; ++t) {
+      const int f = index_host[(long long)i * index_stride + t];
+      VLFB_REQUIRE(f >= 0 && f < store_frames_host[i], "%s: item %d entry %d is frame %d of a store of %d frames", what, i, t, f,
+                   store_frames_host[i]);
+    }
   }
   return VLFB_OK;
 }
@@ -421,4 +469,41 @@ extern "C" int vlfb_clip_batch_preprocess(const vlfb_clip_item* items_host, cons
   else
     VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_batch_preprocess_kernel<T16>, grid, block, 0, (hipStream_t)stream, items_dev));
   return check_launch("clip_batch_preprocess");
+}
+
+extern "C" int vlfb_clip_batch_channel_sums_indexed(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev,
+                                                    int n_items, const int32_t* index_host, const int32_t* index_dev,
+                                                    int index_stride, const int32_t* store_frames_host, vlfb_stream_t stream) {
+  const char* what = "clip_batch_channel_sums_indexed";
+  int frames, tiles;
+  bool any_sums;
+  int rc = check_items(what, items_host, items_dev, n_items, &frames, &tiles, &any_sums);
+  if (rc != VLFB_OK) return rc;
+  rc = check_index(what, items_host, n_items, index_host, index_dev, index_stride, store_frames_host);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(any_sums, "%s: no item has a sums buffer", what);
+  hipLaunchKernelGGL(clip_batch_channel_sums_indexed_kernel, dim3(VLFB_CLIP_SUM_BANDS, frames, n_items), dim3(SUM_THREADS), 0,
+                     (hipStream_t)stream, items_dev, index_dev, index_stride);
+  return check_launch(what);
+}
+
+extern "C" int vlfb_clip_batch_preprocess_indexed(const vlfb_clip_item* items_host, const vlfb_clip_item* items_dev, int n_items,
+                                                  const int32_t* index_host, const int32_t* index_dev, int index_stride,
+                                                  const int32_t* store_frames_host, int dst_dtype, vlfb_stream_t stream) {
+  const char* what = "clip_batch_preprocess_indexed";
+  int frames, tiles;
+  bool any_sums;
+  int rc = check_items(what, items_host, items_dev, n_items, &frames, &tiles, &any_sums);
+  if (rc != VLFB_OK) return rc;
+  rc = check_index(what, items_host, n_items, index_host, index_dev, index_stride, store_frames_host);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(dst_dtype == VLFB_F32 || is16(dst_dtype), "%s: dst dtype must be f32 or bf16", what);
+  const dim3 grid(tiles, frames, n_items), block(TILE_W, TILE_H);
+  if (dst_dtype == VLFB_F32)
+    hipLaunchKernelGGL(clip_batch_preprocess_indexed_kernel<float>, grid, block, 0, (hipStream_t)stream, items_dev, index_dev,
+                       index_stride);
+  else
+    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_batch_preprocess_indexed_kernel<T16>, grid, block, 0, (hipStream_t)stream,
+                                                items_dev, index_dev, index_stride));
+  return check_launch(what);
 }

@@ -190,6 +190,8 @@ _SIGS = {
                                              C.c_int, _P]),
     "vlfb_clip_batch_channel_sums": (C.c_int, [_P, _P, C.c_int, _P]),
     "vlfb_clip_batch_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "vlfb_clip_batch_channel_sums_indexed": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "vlfb_clip_batch_preprocess_indexed": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P]),
     "vlfb_lfb_bank_bytes": (_I64, [C.POINTER(LfbDesc)]),
     "vlfb_lfb_append": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, C.c_int, _P, _I64, _P, _P]),
     "vlfb_lfb_sample_window": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, C.c_uint64,

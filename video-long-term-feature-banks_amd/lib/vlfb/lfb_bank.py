@@ -143,17 +143,42 @@ class DeviceBank(object):
     def append(self, feats, videos, steps):
         """feats: (R, dim[,1,1,1]) device tensor (fp32 / bf16) or host array; videos/steps: (R,) reference
         keys (a negative video marks a padding row)."""
+        self._append_sync(feats, self.append_keys(videos, steps))
+
+    def _append_sync(self, feats, keys):
         if not torch.is_tensor(feats):
             feats = torch.as_tensor(np.asarray(feats, dtype=np.float32))
         feats = feats.to(self.device).reshape(feats.shape[0], -1).contiguous()
         assert feats.shape[1] == self.dim, "append: feature width %d, bank dim %d" % (feats.shape[1], self.dim)
         rows = feats.shape[0]
-        keys = np.stack([self._rows_of(videos), np.asarray(steps).astype(np.int64).reshape(-1) - self.step_base], axis=1)
         assert keys.shape == (rows, 2)
-        kd = self._dev_i32(keys)
+        self.append_enqueue(feats, self._dev_i32(keys), rows)
+        torch.cuda.current_stream().synchronize()     # the keys / feats may be temporaries
+
+    def append_keys(self, videos, steps):
+        """the (rows, 2) int32 keys `append` uploads: [bank row of the video (negative: a padding row), step]"""
+        return np.stack([self._rows_of(videos), np.asarray(steps).astype(np.int64).reshape(-1) - self.step_base],
+                        axis=1).astype(np.int32)
+
+    def frame_keys(self, rows, frame_keys, sample_freq):
+        """`append_keys` of `append_frames`: (video, frame) pairs with (frame + 1) % sample_freq == 0 -> keys of `rows`
+        rows, those beyond len(frame_keys) marked as padding"""
+        fk = np.asarray(frame_keys, dtype=np.int64).reshape(-1, 2)
+        vids = np.full(rows, -1, dtype=np.int64)
+        steps = np.zeros(rows, dtype=np.int64)
+        n = min(rows, fk.shape[0])
+        assert np.all((fk[:n, 1] + 1) % sample_freq == 0), "frame keys must be LFB frames"
+        vids[:n] = fk[:n, 0]
+        steps[:n] = (fk[:n, 1] + 1) // sample_freq - 1
+        return self.append_keys(vids, steps + self.step_base)
+
+    def append_enqueue(self, feats, keys_dev, rows):
+        """`append` for a caller that owns every buffer (a bank-construction pass): feats a contiguous (>= rows, dim) DEVICE
+        tensor (fp32 / bf16), keys_dev the `append_keys` / `frame_keys` it uploaded in stream order.  One launch on the
+        current stream, nothing allocated, no synchronisation."""
+        assert feats.is_cuda and feats.is_contiguous() and feats.numel() >= int(rows) * self.dim
         hip.call("vlfb_lfb_append", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(feats),
-                 hip.dtype_code(feats.dtype), hip.ptr(kd), rows, hip.ptr(self.dropped))
-        torch.cuda.current_stream().synchronize()     # kd / feats may be temporaries
+                 hip.dtype_code(feats.dtype), hip.ptr(keys_dev), int(rows), hip.ptr(self.dropped))
 
     def append_ava(self, box_pooled, metadata):
         """one inference iteration of construct_ava_lfb (lfb_loader.py:79-112): metadata rows are
@@ -165,15 +190,7 @@ class DeviceBank(object):
         """one inference iteration of construct_frame_level_lfb (lfb_loader.py:49-76): frame_keys are
         (video, frame) pairs with (frame + 1) % sample_freq == 0 (charades.py:233-248); rows of
         `pool5` beyond len(frame_keys) are padding"""
-        fk = np.asarray(frame_keys, dtype=np.int64).reshape(-1, 2)
-        rows = pool5.shape[0]
-        vids = np.full(rows, -1, dtype=np.int64)
-        steps = np.zeros(rows, dtype=np.int64)
-        n = min(rows, fk.shape[0])
-        assert np.all((fk[:n, 1] + 1) % sample_freq == 0), "frame keys must be LFB frames"
-        vids[:n] = fk[:n, 0]
-        steps[:n] = (fk[:n, 1] + 1) // sample_freq - 1
-        self.append(pool5, vids, steps + self.step_base)
+        self._append_sync(pool5, self.frame_keys(pool5.shape[0], frame_keys, sample_freq))
 
     def check_no_drops(self):
         n = int(self.dropped.item())
@@ -246,36 +263,61 @@ class DeviceBank(object):
         """Charades (charades.py:251-276): -> (N, window, dim), the first `window` bank frames inside
         [begin, end] around each clip centre, packed to the front"""
         rows = len(videos)
-        lo, hi = frame_window_steps(center_frames, window, clips_per_second)
-        q = np.stack([self._rows_of(videos), lo, hi], axis=1)
-        qd = self._dev_i32(q)
+        qd = self._dev_i32(self.frames_query(videos, center_frames, window, clips_per_second))
         out = self._out(out, (rows, int(window), self.dim), out_dtype)
-        hip.call("vlfb_lfb_sample_compact", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(qd),
-                 rows, int(window), hip.ptr(out), hip.dtype_code(out.dtype))
+        self.sample_compact_enqueue(qd, rows, window, out)
         torch.cuda.current_stream().synchronize()
         return out
 
-    def _sample_packed(self, videos, lo, hi, window, max_per_step, out, out_dtype):
-        rows = len(videos)
-        qd = self._dev_i32(np.stack([self._rows_of(videos), lo, hi], axis=1))
+    def _sample_packed(self, query, window, max_per_step, out, out_dtype):
+        rows = len(query)
+        qd = self._dev_i32(query)
         out = self._out(out, (rows, int(window), self.dim), out_dtype)
-        hip.call("vlfb_lfb_sample_packed", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(qd),
-                 rows, int(window), int(max_per_step), hip.ptr(out), hip.dtype_code(out.dtype))
+        self.sample_packed_enqueue(qd, rows, window, max_per_step, out)
         torch.cuda.current_stream().synchronize()
         return out
+
+    # the (rows, 3) int32 queries [bank row of the video, first step, last step] the three samplers above and below upload
+    def _steps_query(self, videos, lo, hi):
+        return np.stack([self._rows_of(videos), lo, hi], axis=1).astype(np.int32)
+
+    def frames_query(self, videos, center_frames, window, clips_per_second):
+        """the query of `sample_frames`"""
+        return self._steps_query(videos, *frame_window_steps(center_frames, window, clips_per_second))
+
+    def epic_verb_query(self, videos, center_frames, window, clips_per_second=1):
+        """the query of `sample_epic_verb`"""
+        return self._steps_query(videos, *epic_verb_window_steps(center_frames, window, clips_per_second))
+
+    def epic_noun_query(self, videos, center_frames, window, max_per_frame=10, frames_per_second=1):
+        """the query of `sample_epic_noun`"""
+        return self._steps_query(videos, *epic_noun_window_steps(center_frames, window, max_per_frame, frames_per_second))
+
+    def sample_compact_enqueue(self, query_dev, rows, window, out):
+        """`sample_frames` for a caller that owns every buffer (a `frames_query` it uploaded to `query_dev` in stream order,
+        the (rows, window, dim) output): one launch on the current stream, nothing allocated, no synchronisation"""
+        assert out.is_contiguous() and out.numel() >= int(rows) * int(window) * self.dim
+        hip.call("vlfb_lfb_sample_compact", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(query_dev),
+                 int(rows), int(window), hip.ptr(out), hip.dtype_code(out.dtype))
+
+    def sample_packed_enqueue(self, query_dev, rows, window, max_per_step, out):
+        """`sample_epic_verb` (max_per_step 1) / `sample_epic_noun` for a caller that owns every buffer, as
+        `sample_compact_enqueue`"""
+        assert out.is_contiguous() and out.numel() >= int(rows) * int(window) * self.dim
+        hip.call("vlfb_lfb_sample_packed", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(query_dev),
+                 int(rows), int(window), int(max_per_step), hip.ptr(out), hip.dtype_code(out.dtype))
 
     def sample_epic_verb(self, videos, center_frames, window, clips_per_second=1, out=None, out_dtype=None):
         """EPIC-Kitchens verb model (epic.py:310-331): -> (N, window, dim), the first `window` bank clips whose
         centre frame lies within +-(window * FPS) // 2 frames of the clip centre, zero padded"""
-        lo, hi = epic_verb_window_steps(center_frames, window, clips_per_second)
-        return self._sample_packed(videos, lo, hi, window, 1, out, out_dtype)
+        return self._sample_packed(self.epic_verb_query(videos, center_frames, window, clips_per_second), window, 1, out, out_dtype)
 
     def sample_epic_noun(self, videos, center_frames, window, max_per_frame=10, frames_per_second=1, out=None,
                          out_dtype=None):
         """EPIC-Kitchens noun model (epic.py:338-374): detector features, at most `max_per_frame` per bank frame
         in stored order, frames in time order, truncated to `window` rows, zero padded"""
-        lo, hi = epic_noun_window_steps(center_frames, window, max_per_frame, frames_per_second)
-        return self._sample_packed(videos, lo, hi, window, max_per_frame, out, out_dtype)
+        query = self.epic_noun_query(videos, center_frames, window, max_per_frame, frames_per_second)
+        return self._sample_packed(query, window, max_per_frame, out, out_dtype)
 
     @classmethod
     def from_epic(cls, lfb, noun, sample_freq=EPIC_FPS, capacity=None, dtype="bf16", device="cuda:0"):
