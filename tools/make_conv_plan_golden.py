@@ -33,8 +33,9 @@ ALGOS = range(6)
 MAX_BYTES = 770 * 1000
 
 
-def dry_engine(preset, dtype, clips, frames, crop, split, overrides=()):
-    """a dry-run engine as tests/test_lowering.plan builds it, at `clips` clips of frames x crop^2"""
+def dry_engine(preset, dtype, clips, frames, crop, split, overrides=(), share_params_with=None, bank_per_clip=False):
+    """a dry-run engine as tests/test_lowering.plan builds it, at `clips` clips of frames x crop^2; share_params_with: the
+    engine whose parameters it aliases; bank_per_clip: the `lfb` blob with one row per clip (the inference plan of a RoI head)"""
     from vlfb.presets import load_preset
     from core.config import config as cfg
     from models.model_builder_video import ModelBuilder
@@ -54,12 +55,12 @@ def dry_engine(preset, dtype, clips, frames, crop, split, overrides=()):
         sh["labels" + sfx] = (rois, cfg.MODEL.NUM_CLASSES)
         sh["proposals" + sfx] = (rois, 5)
         if "lfb" + sfx in m.input_blob_names:
-            sh["lfb" + sfx] = (rois, cfg.LFB.WINDOW_SIZE * cfg.AVA.LFB_MAX_NUM_FEAT_PER_STEP, 2048)
+            sh["lfb" + sfx] = (clips if bank_per_clip else rois, cfg.LFB.WINDOW_SIZE * cfg.AVA.LFB_MAX_NUM_FEAT_PER_STEP, 2048)
     else:
         sh["labels" + sfx] = (clips, cfg.MODEL.NUM_CLASSES) if cfg.MODEL.MULTI_LABEL else (clips,)
         if "lfb" + sfx in m.input_blob_names:
             sh["lfb" + sfx] = (clips, cfg.LFB.WINDOW_SIZE, 2048)
-    eng = Engine(m, dtype, dry_run=True)
+    eng = Engine(m, dtype, dry_run=True, share_params_with=share_params_with)
     eng.plan(sh)
     return eng
 

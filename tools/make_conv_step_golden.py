@@ -1,13 +1,15 @@
-"""Writes tests/golden/conv_steps.json.gz, the snapshot tests/test_conv_step_golden.py replays: what ConvStep.setup() decides for
+"""Writes the two snapshots tests/test_conv_step_golden.py replays.  tests/golden/conv_steps.json.gz: what ConvStep.setup() decides for
 every conv of the dry-run engines of the benchmarked presets (the matrix of tools/make_conv_plan_golden.py) and of the grouped
 model -- stored descriptors, format flags, operand buffer shapes -- with the engine's scratch requests, the fp16-copy flags
 of the root blobs, the backward order and the plan table; plus one section per engine A/B switch, evaluated in a child process
-with that variable set.  Identical descriptors, step records and lists are stored once and referred to by index.  Needs the
-built library, no GPU.
+with that variable set.  tests/golden/engine_plans.json.gz: what Engine.plan() decides around the convs (record_plan there)
+for those engines and the variants of plan_keys(), with the sections of PLAN_SWITCHES.  Identical descriptors, step / blob
+records and lists are stored once and referred to by index.  Needs the built library, no GPU.
 
-    python tools/make_conv_step_golden.py [--commit ID]
+    python tools/make_conv_step_golden.py [--commit ID] [--only steps|plans]
 
-Regenerate only when a descriptor or a format is MEANT to change; a refactor of ConvStep must pass against the file as it is."""
+Regenerate a file only when what it records is MEANT to change; a refactor of the planner must pass against both as they are.
+The generator is deterministic: on an unchanged engine and with the same --commit it rewrites each file byte for byte."""
 import argparse
 import gzip
 import json
@@ -73,12 +75,44 @@ def steps_snapshot(commit):
         os.path.relpath(snap.GOLDEN, ROOT), commit, sum(len(s) for s in sections.values()), len(steps.rows), len(descs.rows), size))
 
 
+def plans_snapshot(commit):
+    fields = list(cr.FIELDS)
+    descs, rows, lists = Table(), Table(), Table()
+    sections = {"": snap.evaluate(snap.plan_keys(), snap.record_plan)}
+    print("default: %d engines" % len(sections[""]), flush=True)
+    with tempfile.TemporaryDirectory() as tmp:
+        for sw in snap.PLAN_SWITCHES:
+            sections[sw] = snap.evaluate_in_child(snap.switch_keys(), sw, tmp, "plans")
+            print("%s: %d engines" % (sw, len(sections[sw])), flush=True)
+    out = {"commit": commit, "fields": fields, "root_fields": list(snap.ROOT_FIELDS), "sections": {}}
+    for name, sec in sections.items():
+        out["sections"][name] = {}
+        for key, e in sec.items():
+            if "error" in e:
+                out["sections"][name][key] = e
+                continue
+            e = dict(e, attention=[rows.add(dict(a, descs={k: descs.add([d[f] for f in fields]) for k, d in a["descs"].items()}))
+                                   for a in e["attention"]])
+            for k in ("steps", "roots", "pools"):
+                e[k] = [rows.add(r) for r in e[k]]
+            out["sections"][name][key] = {k: lists.add(v) for k, v in e.items()}
+    out.update(descs=descs.rows, rows=rows.rows, lists=lists.rows)
+    size = write(snap.PLANS_GOLDEN, out)
+    print("%s: commit %s, %d engines, %d records, %d lists, %d descriptors, %d bytes" % (
+        os.path.relpath(snap.PLANS_GOLDEN, ROOT), commit, sum(len(s) for s in sections.values()), len(rows.rows), len(lists.rows),
+        len(descs.rows), size))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--commit", default=None, help="commit the snapshot is taken on (default: git rev-parse HEAD)")
+    ap.add_argument("--only", choices=("steps", "plans"), default=None, help="write one of the two files")
     args = ap.parse_args()
     commit = args.commit or subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"]).decode().strip()
-    steps_snapshot(commit)
+    if args.only != "plans":
+        steps_snapshot(commit)
+    if args.only != "steps":
+        plans_snapshot(commit)
 
 
 if __name__ == "__main__":

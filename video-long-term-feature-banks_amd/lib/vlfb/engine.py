@@ -74,6 +74,13 @@ class Blob(object):
         self.planes = None            # "split" dtype: bf16 term planes [2][numel] of the values, written by the producing conv
         self.half = None              # "mix" dtype: fp16 copy of the values for the fp16 backward (root only; Engine.want_half)
         self.need_half = False
+        # properties of the STORAGE, read on the root:
+        self.dead = False             # fused into a conv epilogue by lower_Sum: the storage is never allocated
+        self.is_input = False         # fed from outside (data / labels / proposals / lfb)
+        self.pad_c = 0                # the clip: channels per pixel as stored (0: stored as shaped) ...
+        self.pad_w = 0                # ... and zero pixels on both sides of every W row
+        self.grad_half = False        # "mix": a 16-bit launch reads the fp32 gradient of this blob rounded (GradSlot.half_buf) ...
+        self.grad_half_src = False    # ... and the launch that produces that gradient can leave the rounding
         self.grad_f32 = False         # "mix" dtype: the gradient of this blob is kept in fp32 (theta / phi / g of a non-local block)
         # "mix" dtype: the values are stored as TWO fp16 planes [2][numel] (hi = fp16(v), lo = fp16(v - hi): ~22 bits; vlfb.h
         # VLFB_F16PAIR) instead of fp32 -- what the two-plane forward convs (hip.MATH_F16X3) read without converting anything,
@@ -235,6 +242,12 @@ class Step(object):
         self.inputs = []     # blobs whose gradient this step may produce
         self.outputs = []
         self.params = []     # trainable parameter names whose gradient this step produces
+        self.aux_outputs = []  # blobs this step writes that carry no gradient (the attention probabilities)
+        self._half_post = []   # "mix": outputs whose fp16 copy a copy pass behind this step makes (Engine._plan_half_copies)
+
+    def param_names(self):
+        """the parameters this step may train (None entries: a parameter the layer does not have)"""
+        return ()
 
     def fwd(self):
         raise NotImplementedError
@@ -285,6 +298,10 @@ class ConvStep(Step):
         self.k, self.s, self.p, self.d = kernels, strides, pads, dils
         self.stem = (x.C == 3)
         self.eff_bias = None
+        self.sparse_dgrad = False     # DGRAD as an in-place accumulate over the rows it touches (Engine._plan_sparse_shortcut_dgrads)
+
+    def param_names(self):
+        return (self.wname, self.cbname)
 
     def name(self):
         return "conv:" + self.out.name
@@ -345,7 +362,7 @@ class ConvStep(Step):
         geom = self._geom()
         if self.stem:
             # the data blob is stored with 4 zero pixels on both sides of every W row
-            wpad = getattr(self.x.root, "pad_w", 0) or getattr(self.x, "pad_w", 0)
+            wpad = self.x.root.pad_w
             assert wpad >= self.p[2] and wpad >= self.pack - self.k[2] + self.p[2], "stem needs a W-padded input"
             W = W + 2 * wpad
             geom["pw"] = self.p[2] - wpad
@@ -371,7 +388,7 @@ class ConvStep(Step):
         # split pass over its output gradient).  x_pstride: elements of one plane of the input (W is the padded width here)
         self.x_npl = 2 if (self.x_pair or mf != hip.MATH_BF16X6) else 3
         self.x_pstride = (self.x.root.numel // self.x.root.C // self.x.root.shape[-1] * W * self.Cin_k) if self.stem else self.x.root.numel
-        self.stem_planes = self.stem and (self.x_pair or bool(eng.split and (eng.PLANES or eng.mix) and eng.STEM_PLANES))
+        self.stem_planes = self.stem and (self.x_pair or bool(eng.split and eng.STEM_PLANES))
         has_dgrad = bool(self.x.needs_grad and not self.x.detached)
         assert not (has_dgrad and self.stem)
         # "mix": the gradient arriving at `out` is fp32 (Blob.grad_f32): WGRAD as split-bf16 products on the fp32 operands
@@ -392,23 +409,22 @@ class ConvStep(Step):
         geom_d, rows_d = w2 if (self.w2 and not self.w2i) else (geom, rows_d)
         # (Engine._plan_sparse_shortcut_dgrads) the strided 1x1x1 shortcut as an in-place accumulate over the rows it
         # touches; d_d_full is the ordinary launch, for a pass in which this DGRAD is not an in-place second contribution
-        self._try_sparse = bool(has_dgrad and getattr(self, "sparse_dgrad", False) and not self.bwd_split and not self.dx_f32)
+        self._try_sparse = bool(has_dgrad and self.sparse_dgrad and not self.bwd_split and not self.dx_f32)
         unit = tuple(self.s) == (1, 1, 1)
         plain = unit and tuple(self.k) == (1, 1, 1) and tuple(self.p) == (0, 0, 0)
-        # Pre-split operands ("split" dtype, Engine.PLANES): a conv epilogue can write the bf16 term planes of its output
+        # Pre-split operands ("split" dtype): a conv epilogue can write the bf16 term planes of its output
         # next to the fp32 values (o_planes), and DGRAD / WGRAD launches that find their activation / gradient operands in
         # that form spend no VALU on the expansion (a_planes / p_planes).  Variants are built lazily (_pl_desc).
-        self.dgrad_takes_planes = bool(eng.split and eng.PLANES and G == 1 and (plain or (unit and Cout % 32 == 0)))
+        self.dgrad_takes_planes = bool(eng.split and G == 1 and (plain or (unit and Cout % 32 == 0)))
         # FPROP reads its input as planes too when the forward products are the three-term ones (two planes per operand:
         # the LDS image of the plane DGRAD; six-term products would need three planes of both operands, 96 KiB per stage)
-        self.fprop_takes_planes = bool(eng.split and eng.PLANES and eng.FPROP_PLANES and mf == hip.MATH_BF16X3 and G == 1 and
+        self.fprop_takes_planes = bool(eng.split and mf == hip.MATH_BF16X3 and G == 1 and
                                        not self.stem and (plain or self.Cin_k % 32 == 0))
         self.wcode, self.wf_npl, self.wf_type, self.wd_npl, self.wd_type = self._weight_format(has_dgrad)
-        self.half_by_copy = False       # (True: the fp16 copy of the output comes from a copy pass, Engine._plan_half_copies)
         self.params = [n for n in (self.wname, self.cbname) if n and eng.is_trainable(n)]
         # a conv with a trainable bias (the non-local / FBO convs): the WGRAD launch also produces the bias gradient --
         # db = alpha * s * column sums of the output gradient it reads anyway (vlfb_conv_run_wgrad_bias)
-        fuse_bias = bool(self.cbname and eng.is_trainable(self.cbname) and eng.FUSE_BIAS_GRAD)
+        fuse_bias = bool(self.cbname and eng.is_trainable(self.cbname))
         # dtype / out_dtype / math / alpha / plane fields of the three descriptors
         if self.x_pair:
             fmt_f = dict(dtype=hip.F16, out_dtype=hip.F16 if self.o_pair else hip.F32, math=hip.MATH_F16X3, a_pstride=self.x_pstride,
@@ -455,7 +471,7 @@ class ConvStep(Step):
         wshape = tuple(eng.kernel_shape(self.wname))
         self.w_f = torch.empty(((self.wf_npl,) if self.wf_npl > 1 else ()) + wshape, device=eng.device, dtype=self.wf_type)
         self.w_d = torch.empty(self.wd_npl * _prod(wshape), device=eng.device, dtype=self.wd_type) if self.d_d is not None else None
-        self.x_planes = self.g_planes = None
+        self.x_planes = self.g_planes = self.cb_tmp = None
         if self.stem_planes:
             self.x_planes = torch.empty(self.x_npl * self.x_pstride, device=eng.device, dtype=torch.float16 if self.x_pair else torch.bfloat16)
             if not self.x_pair and self.d_w is not None and not eng.mix:
@@ -740,6 +756,7 @@ class PoolStep(Step):
         self.x, self.out = x, out
         self.inputs, self.outputs = [x], [out]
         self.k, self.s, self.p, self.is_max = kernels, strides, pads, is_max
+        self.two_term_dx = False      # "mix": the fp32 pooled gradient becomes a two-term fp16 input gradient (Engine._analyse_grads)
 
     def name(self):
         return ("maxpool:" if self.is_max else "avgpool:") + self.out.name
@@ -768,7 +785,7 @@ class PoolStep(Step):
     def bwd(self):
         if not self.grad_inputs():
             return
-        if getattr(self, "two_term_dx", False):
+        if self.two_term_dx:
             # "mix": the fp32 pooled gradient -> a two-term fp16 input gradient (Engine._analyse_grads)
             g32, xs = self.out_grad(), self.x.root.slot
 
@@ -813,7 +830,6 @@ class AttentionStep(Step):
         B, Ci, L1 = self.theta.shape
         L2 = self.phi.shape[2]
         self.B, self.Ci, self.L1, self.L2 = B, Ci, L1, L2
-        code, bcode = eng.code, eng.bcode
         self.single = (L1 == 1)
         # One bank per CLIP instead of one copy per RoI (inference): the `lfb` blob was planned with a row per
         # clip, lfb_1x1 and the phi / g convs of every FBO layer run on n_clips x K rows instead of R x K, and a query row
@@ -831,76 +847,80 @@ class AttentionStep(Step):
         if self.single:
             self.ds_ws = torch.empty(B * L2, device=eng.device, dtype=torch.float32)
             return
-        # split math: the B operands (phi, g^T, g, phi^T) are activations, expanded into bf16 term planes by
-        # vlfb_split_planes right before the product that reads them (3 planes forward, 2 backward)
-        mf, mb = eng.math_fwd, eng.math_bwd
-        pl = dict(b_pstride=B * L2 * Ci) if eng.split else {}
-        bpl = pl if mb != hip.MATH_NATIVE else {}                  # ("mix": split forward products, native fp16 backward)
-        self.bsplit = bool(bpl)
-        gemm = lambda dtype=code, **kw: hip.conv_desc(mode=hip.FPROP, dtype=dtype, N=1, Tr=1, Hr=1, Wr=L1, Ts=1, Hs=1,
-                                                      Ws=L1, batch=B, **kw)
-        self.d_s = gemm(out_dtype=hip.F32, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci, o_bstride=L1 * L2, math=mf, **pl)
-        # theta and phi as two fp16 planes (Engine._plan_pairs): the scores are a batched two-plane product (no plane pass over phi,
-        # nothing converted in the loop); the backward reads their hi planes as before
-        self.s_pair = bool(self.theta.root.pair and self.phi.root.pair)
-        assert bool(self.theta.root.pair) == bool(self.phi.root.pair) and not self.g.root.pair
-        if self.s_pair:
-            self.d_s = gemm(dtype=hip.F16, out_dtype=hip.F32, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci, o_bstride=L1 * L2,
-                            math=hip.MATH_F16X3, a_pstride=B * L1 * Ci, b_pstride=B * L2 * Ci)
-        self.o_pair = bool(self.out.root.pair)           # (Engine._plan_pairs: y leaves the P . g product as two fp16 planes)
-        self.d_y = gemm(out_dtype=hip.F16 if self.o_pair else code, Cs=L2, Cn=Ci, a_bstride=L1 * L2, b_bstride=Ci * L2, o_bstride=L1 * Ci, math=mf, **pl)
-        self.d_dp = gemm(dtype=bcode, out_dtype=hip.F32, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci, o_bstride=L1 * L2, math=mb, **bpl)
-        # "mix": dP = dY . g^T as split-bf16 products on fp32 operands (dY through a cast) and the softmax backward on the
-        # fp32 probabilities -- what follows cancels the part of dP that is common to a row
-        self.precise = bool(eng.mix and eng.MIX_NL_F32)
-        if self.precise:
-            self.d_dp = gemm(dtype=hip.F32, out_dtype=hip.F32, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci, o_bstride=L1 * L2,
-                             math=hip.MATH_BF16X3, **pl)
+        self._formats()
+        self._descriptors()
         if eng.split:
             eng.need_scratch_planes(3 * B * L2 * Ci)
-        # fp16: dS = scale * P o (dP - <dP, P>) is ~ 1 / L2 of an activation gradient and would leave the fp16
-        # range (6e-8) for long key axes (1568 keys in 64-frame clips); it is stored times a power of two, which
-        # the two products that consume it divide out again in their epilogues (alpha).  Exact; 1 elsewhere.
-        self.ds_scale = float(16 << max(L2 - 1, 1).bit_length()) if eng.btdtype == torch.float16 else 1.0
-        # ... and the gradients of theta / phi themselves (again ~ 1 / L2 of an activation gradient) are stored
-        # times Blob.grad_scale (set at lowering), which the theta / phi convs divide out (ConvStep.gscale)
-        gs_th, gs_ph = float(self.theta.root.grad_scale), float(self.phi.root.grad_scale)
-        o_th = hip.F32 if self.theta.root.grad_f32 else bcode
-        o_ph = hip.F32 if self.phi.root.grad_f32 else bcode
-        o_g = hip.F32 if self.g.root.grad_f32 else bcode
-        self.d_dth = gemm(dtype=bcode, out_dtype=o_th, Cs=L2, Cn=Ci, a_bstride=L1 * L2, b_bstride=Ci * L2, o_bstride=L1 * Ci,
-                          alpha=gs_th / self.ds_scale, math=mb, **bpl)
-        if o_th == hip.F32 and bcode != hip.F32 and mb == hip.MATH_NATIVE:
+        if self.d_dth.out_dtype == hip.F32 and eng.bcode != hip.F32 and eng.math_bwd == hip.MATH_NATIVE:
             self.theta.root.grad_half_src = True        # (AttentionStep._dtheta: the fp16 rounding next to the fp32 output)
-        # contract over L1: out[L2][Ci] = sum_l P[l][L2] * A[l][Ci]
-        self.d_tn = hip.conv_desc(mode=hip.WGRAD, dtype=bcode, out_dtype=o_g, N=1, Tr=1, Hr=1, Wr=L1, Ts=1,
-                                  Hs=1, Ws=L1, Cs=Ci, Cn=L2, batch=B, a_bstride=L1 * Ci, p_bstride=L1 * L2,
-                                  o_bstride=L2 * Ci, splits=1, math=mb)
-        self.d_tn_phi = hip.conv_desc(mode=hip.WGRAD, dtype=bcode, out_dtype=o_ph, N=1, Tr=1, Hr=1, Wr=L1, Ts=1,
-                                      Hs=1, Ws=L1, Cs=Ci, Cn=L2, batch=B, a_bstride=L1 * Ci, p_bstride=L1 * L2,
-                                      o_bstride=L2 * Ci, splits=1, alpha=gs_ph / self.ds_scale, math=mb)
-        # 16-bit paths: scores + row softmax (and their backward) in one kernel each, the fp32 score matrix never
-        # exists (csrc/vlfb_attn.hip) -- per direction, and only where the library reports the fused kernel as
-        # measured faster; otherwise GEMM -> fp32 scratch -> softmax kernels
-        self.fused_fwd = bool(hip.lib().vlfb_attn_scores_supported(code, L1, L2, Ci) & hip.ATTN_FWD_FASTER) and not self.dot
-        self.fused_bwd = bool(hip.lib().vlfb_attn_scores_supported(bcode, L1, L2, Ci) & hip.ATTN_BWD_FASTER) and \
-            not self.precise and not self.dot
-        if self.dot:
-            # p = theta^T phi / L2 comes straight out of the scores product (alpha), and so does dS = dP / L2 backward
-            self.d_s = gemm(out_dtype=code, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci, o_bstride=L1 * L2, math=mf,
-                            alpha=1.0 / L2, **pl)
-            if self.precise:
-                self.d_dp = gemm(dtype=hip.F32, out_dtype=hip.F32, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci,
-                                 o_bstride=L1 * L2, math=hip.MATH_BF16X3, alpha=self.ds_scale / L2, **pl)
-            else:
-                self.d_dp = gemm(dtype=bcode, out_dtype=bcode, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci,
-                                 o_bstride=L1 * L2, math=mb, alpha=self.ds_scale / L2, **bpl)
         if not (self.fused_fwd and self.fused_bwd):
             eng.need_scratch_f32(B * L1 * L2 + (B * L1 * Ci if self.precise else 0))
         self.dy_f32 = bool(self.out.root.grad_f32)         # ("mix": dY arrives in fp32; the fp16 products read a cast ...
         if self.dy_f32 and not self.single:
             self.out.root.grad_half = True                 # ... or the copy its producer leaves: GradSlot.half_buf)
         eng.need_scratch_act(B * L1 * L2 + B * Ci * L2 + (B * L1 * Ci if self.dy_f32 else 0))
+
+    def _formats(self):
+        """every format decision of the full attention, each taken once"""
+        eng = self.eng
+        L1, L2, Ci = self.L1, self.L2, self.Ci
+        # theta and phi as two fp16 planes (Engine._plan_pairs): the scores are a batched two-plane product (no plane pass over phi,
+        # nothing converted in the loop); the backward reads their hi planes as before
+        self.s_pair = bool(self.theta.root.pair and self.phi.root.pair)
+        assert bool(self.theta.root.pair) == bool(self.phi.root.pair) and not self.g.root.pair
+        self.o_pair = bool(self.out.root.pair)           # (Engine._plan_pairs: y leaves the P . g product as two fp16 planes)
+        # "mix": dP = dY . g^T as split-bf16 products on fp32 operands (dY through a cast) and the softmax backward on the
+        # fp32 probabilities -- what follows cancels the part of dP that is common to a row
+        self.precise = bool(eng.mix and eng.MIX_NL_F32)
+        # split math: the B operands (phi, g^T, g, phi^T) are activations, expanded into bf16 term planes by
+        # vlfb_split_planes right before the product that reads them (3 planes forward, 2 backward; "mix": split forward
+        # products, native fp16 backward)
+        self.bsplit = bool(eng.split and eng.math_bwd != hip.MATH_NATIVE)
+        # fp16: dS = scale * P o (dP - <dP, P>) is ~ 1 / L2 of an activation gradient and would leave the fp16
+        # range (6e-8) for long key axes (1568 keys in 64-frame clips); it is stored times a power of two, which
+        # the two products that consume it divide out again in their epilogues (alpha).  Exact; 1 elsewhere.
+        self.ds_scale = float(16 << max(L2 - 1, 1).bit_length()) if eng.btdtype == torch.float16 else 1.0
+        # 16-bit paths: scores + row softmax (and their backward) in one kernel each, the fp32 score matrix never
+        # exists (csrc/vlfb_attn.hip) -- per direction, and only where the library reports the fused kernel as
+        # measured faster; otherwise GEMM -> fp32 scratch -> softmax kernels
+        self.fused_fwd = bool(hip.lib().vlfb_attn_scores_supported(eng.code, L1, L2, Ci) & hip.ATTN_FWD_FASTER) and not self.dot
+        self.fused_bwd = bool(hip.lib().vlfb_attn_scores_supported(eng.bcode, L1, L2, Ci) & hip.ATTN_BWD_FASTER) and \
+            not self.precise and not self.dot
+
+    def _descriptors(self):
+        """one hip.conv_desc call per product, from the formats _formats chose"""
+        eng = self.eng
+        B, Ci, L1, L2 = self.B, self.Ci, self.L1, self.L2
+        code, bcode, mf, mb = eng.code, eng.bcode, eng.math_fwd, eng.math_bwd
+        pl = dict(b_pstride=B * L2 * Ci) if eng.split else {}
+        bpl = pl if self.bsplit else {}
+        rows = dict(N=1, Tr=1, Hr=1, Wr=L1, Ts=1, Hs=1, Ws=L1, batch=B)
+        # [L1][Ci] x [L2][Ci]^T -> [L1][L2] (scores, dP), [L1][L2] x [Ci][L2]^T -> [L1][Ci] (P . g, d theta); and the
+        # contraction over L1: out[L2][Ci] = sum_l P[l][L2] * A[l][Ci] (d g, d phi)
+        to_keys = dict(mode=hip.FPROP, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, b_bstride=L2 * Ci, o_bstride=L1 * L2, **rows)
+        to_chan = dict(mode=hip.FPROP, Cs=L2, Cn=Ci, a_bstride=L1 * L2, b_bstride=Ci * L2, o_bstride=L1 * Ci, **rows)
+        over_l1 = dict(mode=hip.WGRAD, dtype=bcode, Cs=Ci, Cn=L2, a_bstride=L1 * Ci, p_bstride=L1 * L2, o_bstride=L2 * Ci, splits=1,
+                       math=mb, **rows)
+        if self.dot:
+            # p = theta^T phi / L2 comes straight out of the scores product (alpha), and so does dS = dP / L2 backward
+            fmt_s = dict(dtype=code, out_dtype=code, math=mf, alpha=1.0 / L2, **pl)
+        elif self.s_pair:
+            fmt_s = dict(dtype=hip.F16, out_dtype=hip.F32, math=hip.MATH_F16X3, a_pstride=B * L1 * Ci, b_pstride=B * L2 * Ci)
+        else:
+            fmt_s = dict(dtype=code, out_dtype=hip.F32, math=mf, **pl)
+        fmt_dp = dict(dtype=hip.F32, math=hip.MATH_BF16X3, **pl) if self.precise else dict(dtype=bcode, math=mb, **bpl)
+        if self.dot:
+            fmt_dp.update(alpha=self.ds_scale / L2)
+        # the gradients of theta / phi (again ~ 1 / L2 of an activation gradient) are stored times Blob.grad_scale (set at
+        # lowering), which the theta / phi convs divide out (ConvStep.gscale)
+        gs_th, gs_ph = float(self.theta.root.grad_scale), float(self.phi.root.grad_scale)
+        o_th, o_ph, o_g = (hip.F32 if t.root.grad_f32 else bcode for t in (self.theta, self.phi, self.g))
+        self.d_s = hip.conv_desc(**to_keys, **fmt_s)
+        self.d_y = hip.conv_desc(dtype=code, out_dtype=hip.F16 if self.o_pair else code, math=mf, **to_chan, **pl)
+        self.d_dp = hip.conv_desc(out_dtype=bcode if (self.dot and not self.precise) else hip.F32, **to_keys, **fmt_dp)
+        self.d_dth = hip.conv_desc(dtype=bcode, out_dtype=o_th, alpha=gs_th / self.ds_scale, math=mb, **to_chan, **bpl)
+        self.d_tn = hip.conv_desc(out_dtype=o_g, **over_l1)
+        self.d_tn_phi = hip.conv_desc(out_dtype=o_ph, alpha=gs_ph / self.ds_scale, **over_l1)
 
     def _planes(self, src, nplanes, transpose):
         """bf16 term planes of a (B, L2, Ci) fp32 activation (optionally transposed per batch element): the B
@@ -1102,6 +1122,9 @@ class BNStep(Step):
         self.eps, self.momentum, self.is_test = float(eps), float(momentum), int(bool(is_test))
         self.inputs, self.outputs = [x], [out]
 
+    def param_names(self):
+        return (self.sname, self.bname)
+
     def name(self):
         return "bn:" + self.out.name
 
@@ -1178,6 +1201,7 @@ class DropoutStep(Step):
         Step.__init__(self, eng)
         self.x, self.out, self.ratio = x, out, ratio
         self.inputs, self.outputs = [x], [out]
+        self.seed_slot = None         # slot of this step's seed among the step scalars of a captured / recorded step (Engine.plan)
 
     def name(self):
         return "dropout:" + self.out.name
@@ -1289,9 +1313,10 @@ class ConcatStep(Step):
                 else:
                     # ("mix", fp32 head: a part whose producer keeps an fp16 gradient below an fp32 concat gradient, or the reverse)
                     key = "_part%d" % k
-                    if getattr(self, key, None) is None:
-                        setattr(self, key, torch.empty(self.rows * p.C, device=self.eng.device, dtype=g.dtype))
-                    tmp = getattr(self, key)
+                    tmp = getattr(self, key, None)
+                    if tmp is None:
+                        tmp = torch.empty(self.rows * p.C, device=self.eng.device, dtype=g.dtype)
+                        setattr(self, key, tmp)
 
                     def fn(out, add, mask, o=o, p=p, tmp=tmp):
                         hip.call("vlfb_copy2d", hip.ptr(g) + o * es, self.total, hip.ptr(tmp), p.C, gc, self.rows, p.C)
@@ -1305,6 +1330,9 @@ class FCStep(Step):
         Step.__init__(self, eng)
         self.x, self.out, self.wname, self.bname = x, out, wname, bname
         self.inputs, self.outputs = [x], [out]
+
+    def param_names(self):
+        return (self.wname, self.bname)
 
     def name(self):
         return "fc:" + self.out.name
@@ -1424,7 +1452,6 @@ class Lowering(object):
         self.eng, self.model = eng, model
         self.env = {}
         self.steps = []
-        self.uses = {}          # id(root blob) -> number of consumers seen so far
         self.blobs = OrderedDict()
         self.ssa = ssa_form(model.net.ops)
         # number of readers of every (name, version)
@@ -1498,11 +1525,6 @@ class Lowering(object):
         v = x.view(op.outputs[0], x.shape, x.caxis)
         v.detached = True
         v.needs_grad = False
-        if getattr(x, "is_input", False):
-            v.is_input = True
-            v.pad_c = getattr(x, "pad_c", None)
-            v.pad_w = getattr(x, "pad_w", 0)
-            v.root = x.root
         self.env[op.outputs[0]] = v
         return i + 1
 
@@ -1874,6 +1896,29 @@ class Lowering(object):
         return i + 1
 
 
+class Dataflow(object):
+    """Who writes and who reads every root blob of a step list, built once behind the lowering: the one table the planning
+    passes of the engine look things up in.  A step reads its `inputs` (a conv's residual operand is among them) and
+    writes its `outputs`; roots are keyed by id()."""
+
+    def __init__(self, steps):
+        self.consumers = {}        # root -> [(step index, step, the view it reads)] in step order
+        self.sources = []          # per step: {root it reads: index of the step that wrote it last before this one}
+        self.readers = {}          # step index -> indices of the steps that read one of its outputs, ascending
+        writer = {}
+        for i, st in enumerate(steps):
+            for b in st.inputs:
+                self.consumers.setdefault(id(b.root), []).append((i, st, b))
+            self.sources.append({id(b.root): writer[id(b.root)] for b in st.inputs if id(b.root) in writer})
+            for j in set(self.sources[i].values()):
+                self.readers.setdefault(j, []).append(i)
+            for b in st.outputs:
+                writer[id(b.root)] = i
+
+    def consumers_of(self, blob):
+        return self.consumers.get(id(blob.root), ())
+
+
 # ================================================================================================
 # engine
 # ================================================================================================
@@ -1938,10 +1983,30 @@ class Engine(object):
         self._trainable_set = set(self.trainable)
         self.steps = None
         self.workspace = None
-        self._ws_bytes = 0
-        self._sf32 = 0
-        self._sact = 0
-        self._spl = 0
+        self._ws_bytes = 0             # scratch the steps ask for in setup(): conv workspace bytes, ...
+        self._sf32 = 0                 # ... fp32 elements, ...
+        self._sact = 0                 # ... elements of the backward type, ...
+        self._spl = 0                  # ... bf16 term-plane elements ...
+        self._sjoin = 0                # ... and fp32 elements on the parameter-gradient stream (ConvStep._x_f32)
+        # what plan() decides, in the order its passes run
+        self.env, self.all_blobs = {}, []          # blob name -> Blob (views included); every blob of the lowering
+        self.flow = None                           # Dataflow of the step list
+        self.head_f32, self.head_f32_fbo = [], []  # names of the blobs _plan_head_f32 / _plan_fbo_f32 give an fp32 gradient
+        self.pair_fwd, self.pair_blobs = False, [] # two-plane forward: on at all, and the names of the two-plane blobs
+        self.param_step, self.train_order = {}, [] # trainable name -> its step; the names in backward-completion order
+        self.train_layout, self.frozen_layout = OrderedDict(), OrderedDict()   # name -> (offset, elements, kernel shape)
+        self.shared_params = set()                 # names whose storage belongs to param_owner
+        self.wd_ranges = []                        # [begin, end, weight decay] over flat_param
+        self.stem_mask = None                      # ones on the real taps / channels of the packed stem weight
+        self.bwd_steps = []                        # the steps backward() runs, in its order
+        self.sol_buckets = []                      # _plan_solver_buckets
+        self._bucket_mb = None
+        self._fwd_early, self._fwd_early_set, self._fwd_side = [], set(), set()    # _plan_forward_branches: step indices
+        self._fwd_wait, self._fwd_signal = [], set()
+        self._half_inputs = []                     # "mix": fed blobs whose fp16 copy forward() makes first
+        self._half_pending = False                 # ... and copies on the parameter-gradient stream backward() has to wait for
+        self._drop_steps = []
+        self._wprep = None                         # device tables of vlfb_weight_prep_batched (_build_wprep_tables)
         self.lr = float(model.current_lr)
         self.comm = None
         self.side = None
@@ -1958,6 +2023,7 @@ class Engine(object):
         self._graph_stream = None
         self._eager_steps = 0
         self._trace = None             # recorded step (STEP_TRACE)
+        self._trace_losses = self._graph_losses = ()   # loss steps whose ring a replay pushes
         self.meter = None              # vlfb.metrics.DeviceMeter fed behind every loss head (attach_meter)
         self.meter_labels = None
         self._wq = []                  # parameter-gradient launches waiting for their lag (WGRAD_LAG)
@@ -1989,15 +2055,11 @@ class Engine(object):
     # "mix" dtype: the residual-stream gradient as two fp16 terms (GradSlot.two_term)
     MIX_TRUNK2 = os.environ.get("VLFB_MIX_TRUNK2", "1") != "0"
     # "split" dtype: conv epilogues also write the bf16 term planes of their outputs / input gradients, and the DGRAD / WGRAD
-    # launches that find their operands in that form read them without expanding (ConvStep.bwd); tensors with more than
-    # PLANES_MAX_NUMEL elements (the wide res2 / stem tensors: a second copy costs more HBM time than it saves) stay fp32-only
-    PLANES = True
+    # launches that find their operands in that form read them without expanding (ConvStep.bwd; three-term forward products:
+    # FPROP reads existing input planes as well); tensors with more than PLANES_MAX_NUMEL elements (the wide res2 / stem
+    # tensors: a second copy costs more HBM time than it saves) stay fp32-only
     PLANES_MAX_NUMEL = 52 << 20
-    FPROP_PLANES = True         # three-term forward products: FPROP launches read existing input planes as well
-    PLANES_SCOPE = "gathered"   # "all": planes around every conv, not only the gathered ones (measured)
     STEM_PLANES = True          # conv1: clip and output gradient through a split pass, FPROP / WGRAD on planes
-    # bias gradients of the convs that carry a bias come out of their WGRAD launch (False: a column-sum pass per conv)
-    FUSE_BIAS_GRAD = True
 
     # ---- side stream for parameter gradients ---------------------------------------------------
     class _Side(object):
@@ -2023,38 +2085,8 @@ class Engine(object):
     def on_side_stream(self):
         return Engine._Side(self)
 
-    # Fraction of the CUs the parameter-gradient stream may use (hipExtStreamCreateWithCUMask; 1.0 = an ordinary stream).
-    # The idea: the main stream (forward, dgrad chain) is the critical path of a step and the parameter gradients finish
-    # with ~6 ms of slack, so confining them to a part of the chip would leave the rest to the chain alone.  MEASURED
-    # (round 4, one box, 8 clips): 1.0 -> 455.1 / 452.9 clips/s fp16; 0.875 -> 277.0, 0.75 -> 281.0, 0.625 -> 273.9,
-    # 0.5 -> 273.2, 0.375 -> 245.8; mix 240.3 -> 173.1 (0.75) / 167.7 (0.5).  A masked queue costs far more than it frees
-    # (the whole-row / streaming kernels are sized for one workgroup per CU of the full chip, and the two queues stop
-    # overlapping the way unmasked ones do).  Off; kept as a switch so the measurement can be repeated.
-    SIDE_CU_FRACTION = float(os.environ.get("VLFB_SIDE_CU_FRACTION", "1.0"))
-
     def _make_side_stream(self):
-        frac = float(self.SIDE_CU_FRACTION)
-        if frac >= 1.0:
-            return torch.cuda.Stream(device=self.device)
-        ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        # groups of 8 consecutive mask bits are taken or left whole, spread evenly: whatever the bit -> (XCD, CU) map is
-        # (round-robin over the 8 XCDs or XCD-major), every XCD keeps the same share
-        ngroups = (ncu + 7) // 8
-        take = max(1, int(round(frac * ngroups)))
-        words = [0] * ((ncu + 31) // 32)
-        for k in range(take):
-            gidx = (k * ngroups) // take
-            for b in range(8 * gidx, min(8 * gidx + 8, ncu)):
-                words[b // 32] |= 1 << (b % 32)
-        rt = C.CDLL("libamdhip64.so")
-        stream = C.c_void_p()
-        mask = (C.c_uint32 * len(words))(*words)
-        torch.cuda.set_device(self.device)
-        rc = rt.hipExtStreamCreateWithCUMask(C.byref(stream), C.c_uint32(len(words)), mask)
-        if rc != 0:
-            raise hip.VlfbError("hipExtStreamCreateWithCUMask failed (%d)" % rc)
-        self._side_cu_mask = words
-        return torch.cuda.ExternalStream(stream.value, device=self.device)
+        return torch.cuda.Stream(device=self.device)
 
     # Parameter gradients are leaves of the backward graph: when they run does not matter as long as it is after their
     # output gradient exists (event) and before the all-reduce / solver.  WGRAD_LAG = k issues the parameter gradients of
@@ -2097,9 +2129,13 @@ class Engine(object):
         """run a HOST-side action of a step that is not a library call or a stream edge -- the gradient all-reduces torch issues
         (GradComm), their bookkeeping -- and, while a step is being recorded, append it to the call list so that a replayed
         step re-issues it at the same point between the same kernel launches (Engine.STEP_TRACE on data-parallel steps)"""
-        fn()
         rec = hip.tracing()
+        n = len(rec) if rec is not None else 0
+        fn()
         if rec is not None:
+            # (an action that issued library calls or stream edges of its own would be replayed twice: by them and by this entry)
+            assert len(rec) == n, "traced(%s): the action recorded %d calls of its own" % (name, len(rec) - n)
+
             def call():
                 fn()
                 return 0
@@ -2157,7 +2193,7 @@ class Engine(object):
         self._spl = max(self._spl, int(n))
 
     def need_join_scratch(self, n):
-        self._sjoin = max(getattr(self, "_sjoin", 0), int(n))
+        self._sjoin = max(self._sjoin, int(n))
 
     def join_scratch(self, n):
         """fp32 scratch of the parameter-gradient stream (ConvStep._x_f32)"""
@@ -2204,9 +2240,10 @@ class Engine(object):
         self.plan_roi_rows = any(str(k).startswith("proposals") for k in input_shapes)   # head rows are RoIs, not clips
         low = Lowering(self, self.model, OrderedDict(input_shapes))
         self.steps = low.run()
-        self._plan_head_f32()
         self.env = low.env
         self.all_blobs = list(low.blobs.values())
+        self.flow = Dataflow(self.steps)
+        self._plan_head_f32()
         self._plan_pairs()
         self._plan_params()
         self._analyse_grads()
@@ -2244,10 +2281,6 @@ class Engine(object):
         if len(fcs) != 1:
             return
         writers = (FCStep, DropoutStep, ConcatStep, RoiAlignMaxStep, ConvStep)
-        consumers = {}
-        for st in self.steps:
-            for b in st.inputs:
-                consumers.setdefault(id(b.root), []).append(st)
         work, seen = [fcs[0].x.root], set()
         while work:
             b = work.pop()
@@ -2265,16 +2298,17 @@ class Engine(object):
                 nxt = []
             else:
                 continue
-            if not all(isinstance(c, writers) for c in consumers.get(id(b), [])):
+            cons = [c for _, c, _ in self.flow.consumers_of(b)]
+            if not all(isinstance(c, writers) for c in cons):
                 continue
-            if any(isinstance(c, ConvStep) and (c.group != 1 or c.x.root is not b) for c in consumers.get(id(b), [])):
+            if any(isinstance(c, ConvStep) and (c.group != 1 or c.x.root is not b) for c in cons):
                 continue
             b.grad_f32 = True
             self.head_f32.append(b.name)
             work += nxt
-        self._plan_fbo_f32(consumers)
+        self._plan_fbo_f32()
 
-    def _plan_fbo_f32(self, consumers):
+    def _plan_fbo_f32(self):
         """... and the FBO branch of the head (lfb_helper.py:170-338: reduc conv, lfb_1x1, per layer theta / phi / g, the
         one-query attention, LayerNorm, ReLU, out conv, dropouts, the Sum) between the fp32 concat gradient and the fp32
         RoI features: a dozen fp16 storages in series that left a 2.2e-4 error on the gradient of `box_pooled` -- common
@@ -2282,7 +2316,6 @@ class Engine(object):
         run their backward in fp32 (ConvStep.bwd_split: the split-bf16 DGRAD / WGRAD of the `split` dtype; the other
         steps: their fp32 kernels on the fp32 forward values).  All or nothing: the branch is only marked when every blob
         between the concat and an fp32 slot / a fed blob is produced AND consumed by steps that can do that."""
-        self.head_f32_fbo = []
         f32_ok = lambda st: isinstance(st, (AddStep, DropoutStep, ReluStep, LayerNormStep, ConcatStep)) or \
             (isinstance(st, AttentionStep) and st.theta.shape[2] == 1) or \
             (isinstance(st, ConvStep) and st.group == 1 and not st.stem)    # (incl. an out conv fused with the Sum)
@@ -2300,7 +2333,7 @@ class Engine(object):
                     cand[id(b)] = b
                     work += [i.root for i in st.inputs]
                 for b in cand.values():                # every consumer writes into a slot of the set (or the concat)
-                    for c in consumers.get(id(b), []):
+                    for _, c, _ in self.flow.consumers_of(b):
                         outs_ok = all(id(o.root) in cand or o.root.grad_f32 for o in c.outputs)
                         ok = ok and f32_ok(c) and outs_ok
                 if ok:
@@ -2325,15 +2358,10 @@ class Engine(object):
         self.pair_blobs = []
         if not self.pair_fwd:
             return
-        consumers = {}
-        for st in self.steps:
-            for b in st.inputs:
-                consumers.setdefault(id(b.root), []).append((st, b))
         cand = {}
         for b in self.all_blobs:
             # (an fp32 gradient slot masks with the fp32 VALUES of a post-ReLU blob: those stay fp32)
-            if b.root is not b or b.kind != "act" or getattr(b, "dead", False) or (b.grad_f32 and b.relu) or b.C % 8 or \
-                    getattr(b, "is_input", False):
+            if b.root is not b or b.kind != "act" or b.dead or (b.grad_f32 and b.relu) or b.C % 8 or b.is_input:
                 continue
             st = b.producer
             if (isinstance(st, ConvStep) and st.group == 1 and st.out is b and (not b.grad_f32 or self.PAIR_SCORES)) or \
@@ -2363,8 +2391,8 @@ class Engine(object):
                 elif isinstance(p, ConvStep) and b.grad_f32:
                     # a conv output with an fp32 gradient slot: only theta / phi of a space-time non-local block (the FBO
                     # head's convs run the split-bf16 backward on fp32 VALUES: they keep fp32 storage)
-                    ok = all(isinstance(st, AttentionStep) for st, _ in consumers.get(id(b), []))
-                for st, v in consumers.get(id(b), []):
+                    ok = all(isinstance(st, AttentionStep) for _, st, _ in self.flow.consumers_of(b))
+                for _, st, v in self.flow.consumers_of(b):
                     if isinstance(st, ConvStep):
                         ok = ok and conv_reads(st, b)
                         if st.residual is not None and st.residual.root is b:        # residual and output: one format
@@ -2395,14 +2423,7 @@ class Engine(object):
         seen = set()
         self.param_step = {}
         for st in reversed(self.steps):
-            names = []
-            if isinstance(st, ConvStep):
-                names = [st.wname, st.cbname]
-            elif isinstance(st, FCStep):
-                names = [st.wname, st.bname]
-            elif isinstance(st, BNStep):
-                names = [st.sname, st.bname]
-            for n in names:
+            for n in st.param_names():
                 if n and self.is_trainable(n) and n not in seen:
                     seen.add(n)
                     order.append(n)
@@ -2468,12 +2489,8 @@ class Engine(object):
         if not self.train:
             return
         for st in self.steps:
-            names = []
-            if isinstance(st, ConvStep):
-                names = [st.wname, st.cbname]
-            elif isinstance(st, FCStep):
-                names = [st.wname, st.bname]
-            has_trainable = any(n and self.is_trainable(n) for n in names)
+            # (a BNStep's trainable scale / bias count too: its input is a conv output, which needs a gradient already)
+            has_trainable = any(n and self.is_trainable(n) for n in st.param_names())
             flows = any(b.needs_grad and not b.detached for b in st.inputs)
             for o in st.outputs:
                 o.needs_grad = bool(has_trainable or flows) and o.kind != "i32"
@@ -2529,8 +2546,6 @@ class Engine(object):
                         r.slot.two_term = True
                         st.two_term_dx = True
 
-    SPARSE_SHORTCUT_DGRAD = True
-
     def _plan_sparse_shortcut_dgrads(self):
         """16-bit backward: the DGRAD of a (1, 2, 2)-strided 1x1x1 projection shortcut (res3_0 / res4_0 branch1) reaches only
         the even (h, w) positions of the block input -- three quarters of its output rows are structural zeros that the
@@ -2539,14 +2554,17 @@ class Engine(object):
         accumulate over the rows it touches (hip.ALGO_CLASS0: a quarter of the tiles, nothing else is read or written).
         So: mark those convs and move their backward step behind the other contributor's (they are independent: the
         shortcut's output gradient is the block-output gradient, finished before either runs)."""
-        if not self.SPARSE_SHORTCUT_DGRAD or self.btdtype not in (torch.float16, torch.bfloat16) or (self.split and not self.mix):
+        if self.btdtype not in (torch.float16, torch.bfloat16) or (self.split and not self.mix):
             return
+        live = set(id(st) for st in self.bwd_steps)
         for st in list(self.bwd_steps):
             if not (isinstance(st, ConvStep) and tuple(st.k) == (1, 1, 1) and tuple(st.s) == (1, 2, 2) and tuple(st.p) == (0, 0, 0)
                     and st.group == 1 and st.residual is None and not st.relu and st.x.needs_grad and not st.x.detached):
                 continue
             r = st.x.root
-            others = [o for o in self.bwd_steps if o is not st and any(b.root is r for b in o.grad_inputs())]
+            others = {id(o): o for _, o, v in self.flow.consumers_of(r)
+                      if o is not st and id(o) in live and v.needs_grad and not v.detached}
+            others = list(others.values())
             if r.kind != "act" or r.grad_f32 or r.relu or r.slot.expected != 2 or len(others) != 1 or \
                     not isinstance(others[0], ConvStep) or others[0].x.root is not r or r.shape[3] % 2 or r.shape[4] % 2:
                 continue
@@ -2558,13 +2576,12 @@ class Engine(object):
     def _allocate(self):
         dev = self.device
         for b in self.all_blobs:
-            if b.root is not b or getattr(b, "dead", False):
+            if b.root is not b or b.dead:
                 continue
             if b.kind == "act":
                 n = b.numel
-                if getattr(b, "pad_c", None):
-                    wpad = getattr(b, "pad_w", 0)
-                    n = b.numel // b.C // b.shape[-1] * (b.shape[-1] + 2 * wpad) * b.pad_c
+                if b.pad_c:
+                    n = b.numel // b.C // b.shape[-1] * (b.shape[-1] + 2 * b.pad_w) * b.pad_c
                 b.tensor = torch.zeros(2 * n if b.pair else n, device=dev, dtype=torch.float16 if b.pair else self.tdtype)
             elif b.kind == "f32":
                 b.tensor = torch.zeros(max(b.numel, 1), device=dev, dtype=torch.float32)
@@ -2578,7 +2595,7 @@ class Engine(object):
                     b.slot.buf_lo = torch.zeros(nval, device=dev, dtype=gdt)
                 if b.relu:
                     self.want_half(b)             # the finished gradient is masked by the sign of the values
-                if self.mix and self.GRAD_HALF_COPY and getattr(b, "grad_half", False) and getattr(b, "grad_half_src", False) and \
+                if self.mix and self.GRAD_HALF_COPY and b.grad_half and b.grad_half_src and \
                         b.grad_f32 and b.slot.expected == 1 and not b.relu:       # (a reader that wants it AND a writer that can)
                     b.slot.half_buf = torch.zeros(nval, device=dev, dtype=self.btdtype)       # (GradSlot.half_buf)
             if b.pair:
@@ -2587,14 +2604,14 @@ class Engine(object):
                 b.half = torch.zeros(b.tensor.numel(), device=dev, dtype=torch.float16)
             # "split" dtype: bf16 term planes next to the fp32 values of conv-produced tensors whose consumers are
             # MFMA-bound convs (the large res2 / stem tensors are HBM-bound: a second copy would only cost traffic)
-            if self.split and not self.mix and self.PLANES and self.train and b.kind == "act" and isinstance(b.producer, ConvStep) and \
-                    not getattr(b, "pad_c", None) and b.numel <= self.PLANES_MAX_NUMEL and b.C % 8 == 0:
+            if self.split and not self.mix and self.train and b.kind == "act" and isinstance(b.producer, ConvStep) and \
+                    not b.pad_c and b.numel <= self.PLANES_MAX_NUMEL and b.C % 8 == 0:
                 # ... and only around the gathered convs (3x3, 3x1x1): their WGRAD / DGRAD gain 1.4-1.7x from pre-split
                 # operands, the 1x1x1 layers gain nothing that pays for writing a second copy of their (wide) tensors
-                everywhere = self.PLANES_SCOPE == "all"
-                gathered = lambda st: everywhere or st.k[0] * st.k[1] * st.k[2] > 1
+                # (planes around every conv were measured as well)
+                gathered = lambda st: st.k[0] * st.k[1] * st.k[2] > 1
                 if any(isinstance(st, ConvStep) and st.d_w is not None and st.x.root is b and not st.stem and gathered(st)
-                       for st in self.steps):
+                       for _, st, _ in self.flow.consumers_of(b)):
                     b.planes = torch.zeros(2 * b.numel, device=dev, dtype=torch.bfloat16)
                 if b.slot.expected > 0 and gathered(b.producer):
                     b.slot.planes = torch.zeros(2 * b.numel, device=dev, dtype=torch.bfloat16)
@@ -2604,7 +2621,7 @@ class Engine(object):
                        if b.root is b and b.kind == "act" and b.tensor is not None] + [4])
         self._scratch_act = torch.empty(max(self._sact, biggest), device=dev, dtype=self.btdtype)
         self._scratch_pl = torch.empty(max(self._spl, 8), device=dev, dtype=torch.bfloat16)
-        self._scratch_join = torch.empty(max(getattr(self, "_sjoin", 0), 4), device=dev, dtype=torch.float32)
+        self._scratch_join = torch.empty(max(self._sjoin, 4), device=dev, dtype=torch.float32)
 
     # ---- parameters ---------------------------------------------------------------------------
     def _to_kernel_layout(self, name, arr):
@@ -2642,7 +2659,7 @@ class Engine(object):
         gen = np.random.default_rng(self.base_seed if seed is None else seed)
         out = {}
         for name in list(self.model.params) + list(self.model.computed_params):
-            if name in getattr(self, "shared_params", ()):
+            if name in self.shared_params:
                 continue                      # owned (and initialised / trained) by the engine we share with
             f = self.model.param_init_net.fills[name]
             shape = f.shape
@@ -2717,7 +2734,7 @@ class Engine(object):
 
     def refresh_operands(self, all_params=False):
         """rebuild the MFMA operand copies (one batched launch) and the effective biases"""
-        if getattr(self, "_wprep", None) is None:
+        if self._wprep is None:
             self._build_wprep_tables()
         tab = self._wprep["all" if all_params else "trainable"]
         for dev, n, tiles, wcode in tab or ():
@@ -2732,7 +2749,7 @@ class Engine(object):
         """inputs in the reference layouts (data: (N,3,T,H,W) fp32, labels int32, proposals (R,5),
         lfb (R,K,D) fp32)"""
         b = self.env[name] if name in self.env else None
-        if b is None or not getattr(b.root, "is_input", False) and not getattr(b, "is_input", False):
+        if b is None or not b.root.is_input:
             raise KeyError("%r is not an input blob of this model" % name)
         root = b.root
         t = torch.as_tensor(np.asarray(arr))
@@ -2749,10 +2766,10 @@ class Engine(object):
             root.tensor.copy_(t.to(torch.int32).reshape(-1).to(self.device))
         elif root.kind == "f32":
             root.tensor.copy_(t.to(torch.float32).reshape(-1).to(self.device))
-        elif getattr(root, "pad_c", None):
+        elif root.pad_c:
             src = t.to(torch.float32).contiguous().to(self.device)
             N, Cc = root.shape[0], root.shape[1]
-            wpad = getattr(root, "pad_w", 0)
+            wpad = root.pad_w
             W = root.shape[-1]
             hip.call("vlfb_ncthw_to_nthwc_wpad", hip.ptr(src), root.ptr(), self.code, N, Cc,
                      _prod(root.shape[2:-1]), W, root.pad_c, wpad, W + 2 * wpad)
@@ -2767,9 +2784,9 @@ class Engine(object):
         the host (the feature bank appends `box_pooled` from it and samples into `lfb`).  Row-major
         blobs only: (rows, C[,1,1,1]) activations and (R, K, D) banks are stored exactly as shaped."""
         b = self.env[name].root
-        if getattr(b, "dead", False):
+        if b.dead:
             raise KeyError("blob %r was fused away" % name)
-        if getattr(b, "pad_c", None):
+        if b.pad_c:
             raise KeyError("blob %r is stored padded; use feed()/fetch()" % name)
         spatial = b.shape[2:] if b.caxis == 1 else ()
         if any(int(d) != 1 for d in spatial):
@@ -2782,9 +2799,9 @@ class Engine(object):
         its (pad_w, pad_c): the destination of datasets.data_input_helper.images_and_boxes_preprocessing.
         Padding pixels / the padding channel are zero and must stay zero."""
         b = self.env[name].root
-        if not getattr(b, "pad_c", None):
+        if not b.pad_c:
             raise KeyError("blob %r is not stored padded" % name)
-        wpad = getattr(b, "pad_w", 0)
+        wpad = b.pad_w
         N, T, H, W = b.shape[0], b.shape[2], b.shape[3], b.shape[4]
         n = N * T * H * (W + 2 * wpad) * b.pad_c
         return b.tensor[:n].view(N, T, H, W + 2 * wpad, b.pad_c), (wpad, b.pad_c)
@@ -2794,7 +2811,7 @@ class Engine(object):
         the engine's dtype (R * K * D), data padded as blob_padded describes), for a device-side feeder that copies a whole
         blob in stream order between steps (datasets.clip_loader.MinibatchLoader.deliver).  Anything else is refused."""
         b = self.env[name] if name in self.env else None
-        if b is None or not getattr(b.root, "is_input", False) and not getattr(b, "is_input", False):
+        if b is None or not b.root.is_input:
             raise KeyError("%r is not an input blob of this model" % name)
         if b.root.pair:
             raise KeyError("input blob %r is stored as two planes; use feed()" % name)
@@ -2806,7 +2823,7 @@ class Engine(object):
         if name not in self.env and name.endswith("_grad"):
             name, grad = name[:-5], True
         b = self.env[name]
-        if getattr(b.root, "dead", False):
+        if b.root.dead:
             raise KeyError("blob %r was fused away (its value only exists inside a kernel epilogue)" % name)
         src = b.root.slot.cur if grad else b.root.tensor
         t = src.detach().float().cpu()
@@ -2816,8 +2833,8 @@ class Engine(object):
             t = t / self.loss_scale
         if grad and b.root.grad_scale != 1.0:     # fp16: theta / phi gradients are stored times a power of two
             t = t / b.root.grad_scale
-        if getattr(b.root, "pad_c", None) and not grad:
-            wpad = getattr(b.root, "pad_w", 0)
+        if b.root.pad_c and not grad:
+            wpad = b.root.pad_w
             W = b.shape[-1]
             t = t.view(-1, W + 2 * wpad, b.root.pad_c)[:, wpad:wpad + W, :b.C].reshape(-1)
         order = [ax for ax in range(len(b.shape)) if ax != b.caxis] + [b.caxis]
@@ -2832,7 +2849,7 @@ class Engine(object):
         piecewise-linear network (oracle.model.run(decisions=...)), which separates arithmetic parity from ties at zero."""
         dec = {"relu": {}, "pool": {}, "roi_bin": None}
         for b in self.all_blobs:
-            if b.root is b and b.relu and b.kind == "act" and b.tensor is not None and not getattr(b, "dead", False):
+            if b.root is b and b.relu and b.kind == "act" and b.tensor is not None and not b.dead:
                 dec["relu"][b.name] = self.fetch(b.name) > 0
         for st in self.steps:
             if isinstance(st, PoolStep) and st.is_max and st.argmax is not None:
@@ -2891,14 +2908,12 @@ class Engine(object):
         if st._half_post:                           # "mix": outputs whose fp16 copy no conv epilogue wrote
             self._half_copies(st._half_post)
 
-    # "mix": the copy passes only feed the BACKWARD pass, so they do not have to sit in the forward chain: they run on the
-    # parameter-gradient stream (idle during forward) behind an event of the producer; backward() joins that stream first
-    HALF_COPIES_ON_SIDE = True
-
     def _half_copies(self, blobs):
+        """"mix": the copy passes only feed the BACKWARD pass, so they do not have to sit in the forward chain: they run on the
+        parameter-gradient stream (idle during forward) behind an event of the producer; backward() joins that stream first"""
         cur = torch.cuda.current_stream() if not self.dry_run else None
         # (a captured forward pass has to end with every forked stream joined: the copies stay in the chain there)
-        if self.side is None or not self.HALF_COPIES_ON_SIDE or cur == self.side or self.STEP_GRAPH:
+        if self.side is None or cur == self.side or self.STEP_GRAPH:
             for b in blobs:
                 hip.call("vlfb_half_copy", b.ptr(), hip.ptr(b.half), b.half.numel())
             return
@@ -2914,10 +2929,10 @@ class Engine(object):
         seen = set()
         for st in self.steps:
             st._half_post = []
-            if isinstance(st, ConvStep) and not st.half_by_copy:
+            if isinstance(st, ConvStep):
                 seen.update(id(o.root) for o in st.outputs)
                 continue
-            for o in list(st.outputs) + list(getattr(st, "aux_outputs", ())):
+            for o in st.outputs + st.aux_outputs:
                 r = o.root
                 if r.pair:
                     seen.add(id(r))               # (two planes: the hi plane is the copy)
@@ -2926,7 +2941,7 @@ class Engine(object):
                     st._half_post.append(r)
         self._half_inputs = [b for b in self.all_blobs if b.root is b and b.half is not None and id(b) not in seen]
         for b in self._half_inputs:
-            assert getattr(b, "is_input", False), "blob %s has an fp16 copy that nothing writes" % b.name
+            assert b.is_input, "blob %s has an fp16 copy that nothing writes" % b.name
 
     # independent forward branches on the second stream (Engine.forward)
     FORWARD_BRANCHES = True
@@ -2936,19 +2951,7 @@ class Engine(object):
         """which forward steps run on the second stream, and which cross-stream edges need an event"""
         steps = self.steps
         side = set()
-        writer = {}                                   # id(root blob) -> index of the step that wrote it last
-        writers_at = []                               # per step: {id(root): writer index} of its reads
-        for i, st in enumerate(steps):
-            reads = [b.root for b in st.inputs]
-            if isinstance(st, ConvStep) and st.residual is not None:
-                reads.append(st.residual.root)
-            writers_at.append({id(r): writer[id(r)] for r in reads if id(r) in writer})
-            for b in st.outputs:
-                writer[id(b.root)] = i
-        readers = {}
-        for i, w in enumerate(writers_at):
-            for j in set(w.values()):
-                readers.setdefault(j, []).append(i)
+        writers_at, readers = self.flow.sources, self.flow.readers
         for i, st in enumerate(steps):
             # (a) projection shortcut: a conv whose output is only the residual operand of a later conv, and whose input
             #     feeds another chain as well
@@ -2974,16 +2977,12 @@ class Engine(object):
         if self.FORWARD_BANK_SIDE:
             clip_dep = set()                          # steps that (transitively) read the clip
             for i, st in enumerate(steps):
-                reads = [b.root for b in st.inputs]
-                if isinstance(st, ConvStep) and st.residual is not None:
-                    reads.append(st.residual.root)
-                from_clip = any(getattr(r, "is_input", False) and r.name.startswith("data") for r in reads)
+                from_clip = any(b.root.is_input and b.root.name.startswith("data") for b in st.inputs)
                 if from_clip or any(j in clip_dep for j in writers_at[i].values()):
                     clip_dep.add(i)
             for i, st in enumerate(steps):
-                reads = [b.root for b in st.inputs]
-                if i not in clip_dep and reads and isinstance(st, (ConvStep, DropoutStep)) and \
-                        all(getattr(r, "is_input", False) or writers_at[i].get(id(r)) in early for r in reads):
+                if i not in clip_dep and st.inputs and isinstance(st, (ConvStep, DropoutStep)) and \
+                        all(b.root.is_input or writers_at[i].get(id(b.root)) in early for b in st.inputs):
                     early.append(i)
             side.update(early)
         self._fwd_early = early                       # issued at the start of forward(), in this order
@@ -3003,7 +3002,7 @@ class Engine(object):
                 b.slot.reset()
         del self._wq[:]               # (parameter-gradient launches a failed backward() left queued: WGRAD_LAG)
         self._bwd_index = 0
-        if getattr(self, "_half_pending", False):    # "mix": the fp16 copies made on the parameter-gradient stream
+        if self._half_pending:                       # "mix": the fp16 copies made on the parameter-gradient stream
             self.wait_stream(self.side)
             self._half_pending = False
         if self.comm is not None:
@@ -3069,8 +3068,6 @@ class Engine(object):
     def _solve_bucket(self, b, lr):
         """WeightedSum + MomentumSGDUpdate (model_builder_video.py:348-389) and the MFMA operand refresh for the
         parameters of one bucket, on the current stream"""
-        sol = cfg.SOLVER
-        S = self.loss_scale                       # gradients carry the fp16 loss scale: lr/S * (S g + S wd p)
         for off, end, wd in b["wd"]:
             self._sgd_launch(off, end, wd, lr)
         for dev, n, tiles, wcode in b["wprep"] or ():

@@ -83,8 +83,7 @@ def reference_draw_table(counts, vid, centre, clip_index, window, K, rng):
     prev = None
     for r in range(rows):
         if prev is None or ids[r] != ids[prev]:              # a new clip of the minibatch: its own draw
-            if prev is not None and (vid[r] == vid[prev] and centre[r] == centre[prev]):
-                pass                                         # (the same keyframe again: still a NEW draw, as in the reference)
+            # (even when it names the same keyframe as the clip before it: still a NEW draw, as in the reference)
             t = np.full((int(window), int(K)), -1, dtype=np.int32)
             lower = int(centre[r]) - int(window) // 2
             for j in range(int(window)):
