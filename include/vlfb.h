@@ -470,6 +470,13 @@ int vlfb_softmax_ce(const float* logits, const int32_t* labels, float* prob, flo
  * RoI head.  Replaces RoIAlign + 7x7 MaxPool (head_helper.py:88-123, lfb_helper.py:130-152).
  * feat: [N,H,W,C] channels-last `dtype`; rois: fp32 (R,5) = [batch_idx, x1,y1,x2,y2];
  * out: [R,C] = max over the pooled x pooled RoIAlign bins; argbin: uint8 [R,C].
+ * argbin is the FIRST maximal bin in row-major bin order (bin = ph * pooled + pw): bins are accumulated in fp32 (from the
+ * 16-bit values too) in the operator's sample / corner order and compared with a strict >, within a group of pooled rows and
+ * again when the groups are folded, so equal maxima -- channels that are zero over a whole RoI, bins whose samples all
+ * clamp to the same border pixel -- resolve as a serial scan does, whatever the channel count.  A RoI with no sample
+ * inside the map gives out = 0, argbin = 0.  Every batch index must lie in [0, n): it is not checked.
+ * Rejected without launching anything (VLFB_ERR_ARG): c not a multiple of the 16-byte vector (4 fp32 / 8 16-bit
+ * elements), more than 1024 such vectors per row, pooled * pooled > 255, r <= 0, an unknown dtype.
  * dbg (optional, int32 [R][pooled][pooled][8]) receives the integer decisions of the first
  * sample of every bin: {batch, grid_h, grid_w, y_low, x_low, y_high, x_high, inside}.
  * ------------------------------------------------------------------------------------------ */
