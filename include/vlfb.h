@@ -10,7 +10,9 @@
  *   - plain pointers + sizes only; no torch / HIP types in signatures (vlfb_stream_t is a
  *     hipStream_t passed as void*).
  *   - the caller owns every buffer; kernels are asynchronous on `stream`; the library
- *     allocates nothing and keeps no mutable global state besides a thread-local error string.
+ *     allocates nothing.  Its only state: a thread-local error string, a thread-local conv plan cache, launch
+ *     attributes set once per process and kernel, and environment switches and device properties read once
+ *     (all once-initialised, thread-safe); any number of threads may call it concurrently.
  *   - every function returns VLFB_OK (0) or a negative error code; vlfb_last_error() gives text.
  *   - "NCTHW" = the reference's blob layout (kwargs['order']='NCHW',
  *     lib/models/model_builder_video.py:69).  "NTHWC" = this library's internal

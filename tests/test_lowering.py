@@ -2,6 +2,7 @@
 recorded reference ops as designed, gradients are routed to the right tensors, and the flat
 parameter buckets follow backward-completion order."""
 import collections
+import math
 
 import pytest
 
@@ -425,3 +426,22 @@ def test_two_plane_storage_stops_at_the_fp32_head_with_and_without_dropout():
         for st in eng.steps:
             if isinstance(st, ConvStep) and st.bwd_split:
                 assert not st.x_pair and not st.o_pair, st.out.name
+
+
+def test_weight_formats_table_covers_the_snapshot():
+    """hip.WEIGHT_FORMATS is the one statement of what a weight code means on the host: it has exactly the codes the engines
+    of the conv-step snapshot use, and every conv step of the snapshot holds its operand copies as the table says -- plane
+    counts and element types of the FPROP copy, and of the DGRAD copy where the step keeps one.  (A conv without a DGRAD
+    copy has nothing to compare there: the snapshot records w_d = None for it.)"""
+    import test_conv_step_golden as golden
+    from vlfb import hip
+    assert set(hip.WEIGHT_FORMATS) == set(golden.WCODES(hip))
+    g, sections = golden.load()
+    steps = g["steps"]
+    assert len(steps) > 500 and any(s["w_d"] is None for s in steps)
+    for s in steps:
+        wf_npl, wf_type, wd_npl, wd_type = hip.WEIGHT_FORMATS[s["wcode"]]
+        block = s["wblk"] * s["group"]                    # elements of one plane
+        assert s["wf_npl"] == wf_npl and s["w_f"][1] == str(wf_type) and math.prod(s["w_f"][0]) == wf_npl * block, s["name"]
+        if s["w_d"] is not None:
+            assert s["wd_npl"] == wd_npl and s["w_d"][1] == str(wd_type) and math.prod(s["w_d"][0]) == wd_npl * block, s["name"]

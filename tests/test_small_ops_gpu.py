@@ -691,6 +691,101 @@ def test_weight_prep_batched_two_term_formats_through_the_engine_table_builder(f
             assert ((back - v).abs() <= torch.clamp(v.abs() * 2.0 ** -21, min=2.0 ** -24)).all(), "DGRAD terms"
 
 
+# every weight code is a pair (FPROP copy, DGRAD copy), include/vlfb.h: "elem" = elements of the code's own type, "bf16x3" /
+# "bf16x2" = bf16 term planes, "h2" = two fp16 planes of v * 2^10, "f16" = fp16 elements, "w2" / "w2i" = two fp16 terms of
+# v * 2^10 as [Cin][term][taps][Cout] / interleaved [Cin][taps][Cout / 64][term][64]
+WFORMATS = {"F32": ("elem", "elem"), "F16": ("elem", "elem"), "BF16": ("elem", "elem"), "SPLIT": ("bf16x3", "bf16x2"),
+            "MIX": ("bf16x3", "f16"), "MIX_W2": ("bf16x3", "w2"), "MIX_W2I": ("bf16x3", "w2i"),
+            "MIXH": ("h2", "f16"), "MIXH_W2": ("h2", "w2"), "MIXH_W2I": ("h2", "w2i")}
+WFORMAT_ITEMS = [(64, 9, 4, True, True), (128, 3, 64, True, True), (192, 1, 40, False, True)]      # Cout % 64 == 0
+WFORMAT_ITEMS_ANY_COUT = [(33, 1, 31, True, False), (40, 3, 72, True, True)]
+
+
+def wformat_bytes(kind, v, elem):
+    """the bytes of one weight operand copy of the fp32 values v (already in the copy's [a][taps][b] order), by definition"""
+    from conv_desc_ref import bf16_terms, f16_pair, w2i_rows
+    if kind == "elem":
+        t = v.to(elem)
+    elif kind == "f16":
+        t = v.half()
+    elif kind in ("bf16x3", "bf16x2"):
+        t = torch.stack(bf16_terms(v, int(kind[-1])))
+    elif kind == "h2":
+        t = torch.stack(f16_pair(v * hip.MIX_W2_SCALE))
+    elif kind == "w2":
+        t = torch.stack(f16_pair(v * hip.MIX_W2_SCALE), 1)                     # [Cin][term][taps][Cout]
+    else:
+        t = w2i_rows((v * hip.MIX_W2_SCALE).reshape(-1, v.shape[-1]))[0]       # rows (Cin, tap) of [Cout / 64][term][64]
+    return t.contiguous().view(-1).view(torch.uint8)
+
+
+@pytest.mark.parametrize("fmt", sorted(WFORMATS))
+def test_weight_prep_formats_batched_and_per_item(fmt):
+    """All ten weight codes: the batched launch writes, per item and copy, exactly the bytes vlfb_weight_prep writes, those
+    are the format's definition applied to the fp32-rounded w * s (tests/conv_desc_ref.py: bf16_terms, f16_pair, w2i_rows),
+    and the bytes between and behind the outputs keep their sentinel."""
+    wcode = getattr(hip, fmt)
+    f_kind, d_kind = WFORMATS[fmt]
+    elem = hip.TORCH_DTYPE.get(wcode)
+    size = lambda kind: {"elem": elem.itemsize if elem else 0, "f16": 2, "bf16x3": 6, "bf16x2": 4, "h2": 4, "w2": 4, "w2i": 4}[kind]
+    cases = WFORMAT_ITEMS + ([] if d_kind == "w2i" else WFORMAT_ITEMS_ANY_COUT)
+    gen = torch.Generator().manual_seed(61)
+    GAP, FILL = 48, 0xA5                                       # sentinel bytes between and behind the outputs (16-byte steps)
+    total = sum(c * t * i * (size(f_kind) + (size(d_kind) if d else 0)) + GAP * (2 if d else 1) for c, t, i, _, d in cases)
+    out = torch.full((total,), FILL, device=dev(), dtype=torch.uint8)
+    items, where, tile, off = [], [], 0, 0
+    for cout, taps, cin, has_s, has_d in cases:
+        w = torch.randn(cout, taps, cin, generator=gen) * 0.07
+        s = torch.rand(cout, generator=gen) + 0.5 if has_s else None
+        W, S = gpu(w), (gpu(s) if has_s else None)
+        _KEEP.extend([W, S])
+        n = cout * taps * cin
+        it = hip.WPrepItem()
+        it.w, it.scale = W.data_ptr(), (S.data_ptr() if has_s else None)
+        it.w_fprop, f_off = out.data_ptr() + off, off
+        off += n * size(f_kind) + GAP
+        it.w_dgrad, d_off = (out.data_ptr() + off, off) if has_d else (None, None)
+        off += (n * size(d_kind) + GAP) if has_d else 0
+        it.cout, it.taps, it.cin, it.tile_begin = cout, taps, cin, tile
+        tile += wprep_tiles(cout, taps, cin)
+        items.append(it)
+        where.append((w, s, W, S, f_off, d_off))
+    assert off == total
+    hip.call("vlfb_weight_prep_batched", hip.ptr(items_to_device(items)), len(items), tile, wcode)
+    got = out.cpu()
+    covered = torch.zeros(total, dtype=torch.bool)
+    for (cout, taps, cin, has_s, has_d), (w, s, W, S, f_off, d_off) in zip(cases, where):
+        n = cout * taps * cin
+        nf, nd = n * size(f_kind), n * size(d_kind)
+        wf1 = torch.full((nf + GAP,), FILL, device=dev(), dtype=torch.uint8)
+        wd1 = torch.full((nd + GAP,), FILL, device=dev(), dtype=torch.uint8) if has_d else None
+        hip.call("vlfb_weight_prep", hip.ptr(W), hip.ptr(S), hip.ptr(wf1), hip.ptr(wd1), wcode, cout, taps, cin)
+        ws = (w * s.view(-1, 1, 1)) if has_s else w              # the fp32-rounded product the formats are defined on
+        for kind, v, o, nb, one in ((f_kind, ws, f_off, nf, wf1),) + (((d_kind, ws.permute(2, 1, 0).contiguous(), d_off, nd, wd1),) if has_d else ()):
+            one = one.cpu()
+            assert torch.equal(one[:nb], got[o:o + nb]), (cout, taps, cin, kind, "batched != per item")
+            assert bool((one[nb:] == FILL).all()), (cout, taps, cin, kind, "vlfb_weight_prep wrote behind its output")
+            assert torch.equal(one[:nb], wformat_bytes(kind, v, elem)), (cout, taps, cin, kind, "not the format's definition")
+            covered[o:o + nb] = True
+    rest = got[~covered]
+    assert rest.numel() == GAP * (len(cases) + sum(1 for c in cases if c[4]))
+    assert bool((rest == FILL).all()), "memory between / behind the outputs was written"
+
+
+def test_weight_prep_rejects_what_is_not_a_weight_code():
+    """VLFB_F16PAIR (8) names two-plane tensors, not a weight format; 11 is past the last code"""
+    W = gpu(torch.ones(64, 1, 64))
+    out = sentinel((2 * 3 * 64 * 64,), torch.float32)
+    it = hip.WPrepItem()
+    it.w, it.scale, it.w_fprop, it.w_dgrad = W.data_ptr(), None, out.data_ptr(), None
+    it.cout, it.taps, it.cin, it.tile_begin = 64, 1, 64, 0
+    tab = items_to_device([it])
+    for code in (hip.F16PAIR, 11, -1):
+        rejected("vlfb_weight_prep", hip.ptr(W), None, hip.ptr(out), None, code, 64, 1, 64, match="weight_prep: bad dtype")
+        rejected("vlfb_weight_prep_batched", hip.ptr(tab), 1, wprep_tiles(64, 1, 64), code, match="weight_prep_batched: bad dtype")
+    assert float(out.min()) == -77.0 and float(out.max()) == -77.0
+
+
 # ------------------------------------------------------------------------------------------------
 # vlfb_ncthw_to_nthwc / vlfb_nthwc_to_ncthw
 # ------------------------------------------------------------------------------------------------

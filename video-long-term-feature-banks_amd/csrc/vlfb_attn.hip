@@ -407,45 +407,33 @@ __global__ __launch_bounds__(512) void attn_qrows_kernel(const AttnP p) {
   }
 }
 
+template <bool BWD> constexpr const char* kAttnWhat = BWD ? "attn_scores_bwd" : "attn_scores_fwd";
+
 template <typename T, bool BWD>
-void launch_attn_q(const AttnP& p, long long batch, hipStream_t s) {
-  static bool configured = false;       // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_qrows_kernel<T, BWD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL((attn_qrows_kernel<T, BWD>), dim3((unsigned)((p.L1 + 127) / 128), (unsigned)batch), dim3(512),
-                     (size_t)3 * 49 * 16 * 64 + 7 * 1024, s, p);
+int launch_attn_q(const AttnP& p, long long batch, hipStream_t s) {
+  return launch_lds<attn_qrows_kernel<T, BWD>, 160 * 1024>(dim3((unsigned)((p.L1 + 127) / 128), (unsigned)batch), dim3(512),
+                                                           (size_t)3 * 49 * 16 * 64 + 7 * 1024, s, kAttnWhat<BWD>, p);
 }
 
 template <typename T, int FN, bool BWD>
-void launch_attn(const AttnP& p, long long batch, hipStream_t s) {
+int launch_attn(const AttnP& p, long long batch, hipStream_t s) {
   constexpr size_t tile = 64 * (size_t)(8 * 16 * FN * 2 + 16);
   const size_t q = (size_t)64 * p.Ci * 2;
   const size_t lds = (tile > q ? tile : q) + 8 * 64 * 4;
-  static bool configured = false;       // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_rows_kernel<T, FN, BWD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL((attn_rows_kernel<T, FN, BWD>), dim3((unsigned)((p.L1 + 63) / 64), (unsigned)batch), dim3(512), lds, s, p);
+  return launch_lds<attn_rows_kernel<T, FN, BWD>, 160 * 1024>(dim3((unsigned)((p.L1 + 63) / 64), (unsigned)batch), dim3(512), lds, s,
+                                                              kAttnWhat<BWD>, p);
 }
 
 template <bool BWD>
 int run_attn(const AttnP& p, int dtype, long long batch, hipStream_t s) {
+  int rc;
   if (p.L2 == 784 && p.Ci == 256) {     // queries-per-wave tiling (res3 non-local blocks of a 32 x 224^2 clip)
-    if (dtype == VLFB_F16) launch_attn_q<f16_t, BWD>(p, batch, s); else launch_attn_q<bf16_t, BWD>(p, batch, s);
-    return check_launch(BWD ? "attn_scores_bwd" : "attn_scores_fwd");
+    VLFB_WITH_T16(dtype, rc = launch_attn_q<T16, BWD>(p, batch, s));
+    return rc;
   }
   const bool wide = p.L2 > 896;
-  if (dtype == VLFB_F16) {
-    if (wide) launch_attn<f16_t, 8, BWD>(p, batch, s); else launch_attn<f16_t, 7, BWD>(p, batch, s);
-  } else {
-    if (wide) launch_attn<bf16_t, 8, BWD>(p, batch, s); else launch_attn<bf16_t, 7, BWD>(p, batch, s);
-  }
-  return check_launch(BWD ? "attn_scores_bwd" : "attn_scores_fwd");
+  VLFB_WITH_T16(dtype, rc = wide ? launch_attn<T16, 8, BWD>(p, batch, s) : launch_attn<T16, 7, BWD>(p, batch, s));
+  return rc;
 }
 
 bool supported(int dtype, long long l1, long long l2, long long ci) {

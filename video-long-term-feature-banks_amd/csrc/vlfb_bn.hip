@@ -190,23 +190,22 @@ extern "C" int vlfb_bn_fwd(const void* x, void* y, const float* gamma, const flo
   float* partial = (float*)workspace;
   float* coef = partial + (int64_t)slabs * 2 * C;
   const dim3 cgrid((unsigned)((C + 255) / 256));
+  // (check: dtype is one of the three element types)
   if (is_test) {
     hipLaunchKernelGGL(bn_fold_test_kernel, cgrid, dim3(256), 0, s, (int)C, gamma, beta, running_mean, running_var, coef, eps);
   } else {
     const dim3 grid((unsigned)((C / v + kCL - 1) / kCL), (unsigned)slabs);
-    if (dtype == VLFB_F32) {
-      hipLaunchKernelGGL((bn_partial_kernel<float, false>), grid, dim3(256), 0, s, (const float*)x, nullptr, nullptr, nullptr, (long long)rows, (int)C, partial);
-      hipLaunchKernelGGL(bn_finish_train_kernel<float>, cgrid, dim3(256), 0, s, partial, slabs, (const float*)x, (long long)rows, (int)C, gamma, beta, running_mean, running_var, save_mean, save_inv_std, coef, eps, momentum);
-    } else {
-      VLFB_WITH_T16(dtype, hipLaunchKernelGGL((bn_partial_kernel<T16, false>), grid, dim3(256), 0, s, (const T16*)x, nullptr, nullptr, nullptr, (long long)rows, (int)C, partial);
-                    hipLaunchKernelGGL(bn_finish_train_kernel<T16>, cgrid, dim3(256), 0, s, partial, slabs, (const T16*)x, (long long)rows, (int)C, gamma, beta, running_mean, running_var, save_mean, save_inv_std, coef, eps, momentum));
-    }
+    with_elem(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((bn_partial_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, nullptr, nullptr, nullptr, (long long)rows, (int)C, partial);
+      hipLaunchKernelGGL(bn_finish_train_kernel<T>, cgrid, dim3(256), 0, s, partial, slabs, (const T*)x, (long long)rows, (int)C, gamma, beta, running_mean, running_var, save_mean, save_inv_std, coef, eps, momentum);
+    });
   }
   const int agrid = grid_for(rows * (C / v), 256);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL((bn_apply_kernel<float, false>), dim3(agrid), dim3(256), 0, s, (const float*)x, nullptr, (float*)y, coef, (long long)rows, (int)C);
-  else
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL((bn_apply_kernel<T16, false>), dim3(agrid), dim3(256), 0, s, (const T16*)x, nullptr, (T16*)y, coef, (long long)rows, (int)C));
+  with_elem(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_apply_kernel<T, false>), dim3(agrid), dim3(256), 0, s, (const T*)x, nullptr, (T*)y, coef, (long long)rows, (int)C);
+  });
   return check_launch("bn_fwd");
 }
 
@@ -224,17 +223,17 @@ extern "C" int vlfb_bn_bwd(const void* dy, const void* x, const float* gamma, co
   float* coef = partial + (int64_t)slabs * 2 * C;
   const dim3 grid((unsigned)((C / v + kCL - 1) / kCL), (unsigned)slabs);
   const dim3 cgrid((unsigned)((C + 255) / 256));
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL((bn_partial_kernel<float, true>), grid, dim3(256), 0, s, (const float*)x, (const float*)dy, save_mean, save_inv_std, (long long)rows, (int)C, partial);
-  else
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL((bn_partial_kernel<T16, true>), grid, dim3(256), 0, s, (const T16*)x, (const T16*)dy, save_mean, save_inv_std, (long long)rows, (int)C, partial));
+  with_elem(dtype, [&](auto t) {          // (check: dtype is one of the three element types)
+    using T = decltype(t);
+    hipLaunchKernelGGL((bn_partial_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, save_mean, save_inv_std, (long long)rows, (int)C, partial);
+  });
   hipLaunchKernelGGL(bn_finish_grad_kernel, cgrid, dim3(256), 0, s, partial, slabs, (long long)rows, (int)C, gamma, save_mean, save_inv_std, dgamma, dbeta, coef, grad_scale);
   if (dx) {
     const int agrid = grid_for(rows * (C / v), 256);
-    if (dtype == VLFB_F32)
-      hipLaunchKernelGGL((bn_apply_kernel<float, true>), dim3(agrid), dim3(256), 0, s, (const float*)x, (const float*)dy, (float*)dx, coef, (long long)rows, (int)C);
-    else
-      VLFB_WITH_T16(dtype, hipLaunchKernelGGL((bn_apply_kernel<T16, true>), dim3(agrid), dim3(256), 0, s, (const T16*)x, (const T16*)dy, (T16*)dx, coef, (long long)rows, (int)C));
+    with_elem(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((bn_apply_kernel<T, true>), dim3(agrid), dim3(256), 0, s, (const T*)x, (const T*)dy, (T*)dx, coef, (long long)rows, (int)C);
+    });
   }
   return check_launch("bn_bwd");
 }

@@ -31,6 +31,38 @@ inline int check_launch(const char* what) {
 #define VLFB_REQUIRE(cond, ...) \
   do { if (!(cond)) return ::vlfb::set_error(VLFB_ERR_ARG, __VA_ARGS__); } while (0)
 
+// ---- element-type dispatch ----------------------------------------------------------------
+// f(T{}) with the element type `dtype` names (float, f16_t, bf16_t); false, and no call, for any other code.  A call site
+// states its kernel once:  with_elem(dtype, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL(kernel<T>, ...); })
+template <typename F>
+inline bool with_elem(int dtype, F&& f) {
+  switch (dtype) {
+    case VLFB_F32: f(float{}); return true;
+    case VLFB_F16: f(f16_t{}); return true;
+    case VLFB_BF16: f(bf16_t{}); return true;
+    default: return false;
+  }
+}
+// f(I{}) with the arg-max index type of a max pool: uint8_t, or uint16_t for windows of more than 255 taps
+template <typename F>
+inline void with_argmax(bool wide, F&& f) {
+  if (wide) f(uint16_t{}); else f(uint8_t{});
+}
+
+// ---- launch of a kernel that needs more dynamic LDS than the 64 KiB default ---------------
+// The limit is raised once per process and KERNEL (the kernel is a template argument, so kernels of one function type do
+// not share the flag) through a function-local static -- thread-safe -- whose hipError_t is kept: a failure is reported
+// by every launch of that kernel instead of surfacing later as an unexplained launch error.
+template <auto Kernel, int MaxLdsBytes, typename... Args>
+inline int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const char* what, Args... args) {
+  static const hipError_t raised =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MaxLdsBytes);
+  if (raised != hipSuccess)
+    return set_error(VLFB_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(raised));
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+  return check_launch(what);
+}
+
 // A/B switches: integer environment variables.  Every site keeps its value in a `static const`, so a switch is read once
 // per process; names, defaults and meanings are listed in DESIGN.md section 5.
 inline int env_int(const char* name, int dflt) {
@@ -125,6 +157,18 @@ template <> struct Vec16<f16_t> : Vec16x16bit<f16_t> {};
 // vlfb_ops.hip: column sums without atomics -- per-slab partial rows that the caller folds in a fixed order
 int colsum_slabs(int dtype, long long rows, long long cols);
 int colsum_partials(const void* g, int dtype, long long rows, long long cols, long long ld, float* partials, hipStream_t s);
+
+// compute units of the current device, rounded down to whole groups of 8 (256 where the query fails): the workgroup count
+// of the persistent kernels.  Read once per process.
+inline int device_cus8() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
+    return n / 8 * 8;
+  }();
+  return ncu;
+}
 
 inline int grid_for(int64_t work_items, int block, int cap = 256 * 16) {
   int64_t g = (work_items + block - 1) / block;

@@ -198,16 +198,10 @@ __global__ __launch_bounds__(512) void conv_rows64_kernel(const GP p, const int 
   }
 }
 
-template <typename K>
-int launch_rows64(K kernel, const GP& gp, int nks, int nframes, int fpw, unsigned nwg, hipStream_t s) {
-  static bool configured = false;   // per template instance
+template <auto Kernel>
+int launch_rows64(const GP& gp, int nks, int nframes, int fpw, unsigned nwg, hipStream_t s) {
   const size_t lds = (size_t)nks * 4096 + kRing * kRowPitch + 256;
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(512), lds, s, gp, nframes, fpw);
-  return check_launch("conv kernel (64-channel rows, direct)");
+  return launch_lds<Kernel, 160 * 1024>(dim3(nwg), dim3(512), lds, s, "conv kernel (64-channel rows, direct)", gp, nframes, fpw);
 }
 
 }  // namespace
@@ -229,20 +223,14 @@ bool conv_rows64_ok(const GP& gp, int mode, int dtype, int out_dtype, long long 
 }
 
 int launch_conv_rows64(const GP& gp, int mode, int dtype, hipStream_t s) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    ncu = n / 8 * 8;
-  }
+  const int ncu = device_cus8();
   const bool tm = gp.kt == 3;
   const int nframes = tm ? gp.M / (gp.Tr * gp.Wr) : gp.M / (gp.Hr * gp.Wr);      // (n, h) slabs | (n, t) frames
   long long nwg = ((long long)nframes + 7) / 8 * 8;
   if (nwg > ncu) nwg = ncu;
   const int fpw = (int)((nframes + nwg - 1) / nwg);
   const bool dg = mode == VLFB_CONV_DGRAD;
-#define VLFB_ROWS64(T_, DG_, TM_) launch_rows64(conv_rows64_kernel<T_, DG_, TM_>, gp, TM_ ? 6 : 18, nframes, fpw, (unsigned)nwg, s)
+#define VLFB_ROWS64(T_, DG_, TM_) launch_rows64<conv_rows64_kernel<T_, DG_, TM_>>(gp, TM_ ? 6 : 18, nframes, fpw, (unsigned)nwg, s)
   if (dtype == VLFB_F16) {
     if (tm) return dg ? VLFB_ROWS64(f16_t, true, true) : VLFB_ROWS64(f16_t, false, true);
     return dg ? VLFB_ROWS64(f16_t, true, false) : VLFB_ROWS64(f16_t, false, false);

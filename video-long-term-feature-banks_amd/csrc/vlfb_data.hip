@@ -409,10 +409,10 @@ extern "C" int vlfb_clip_preprocess_color(const vlfb_clip_desc* d, const vlfb_cl
   const int rq = color_params("clip_preprocess_color", c, sums, &q);
   if (rq != VLFB_OK) return rq;
   const dim3 grid(grid_for((int64_t)p.crop_h * p.crop_w, 256, 256), p.T);
-  if (dst_dtype == VLFB_F32)
-    hipLaunchKernelGGL(clip_preprocess_color_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p, q, (float*)dst);
-  else
-    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_preprocess_color_kernel<T16>, grid, dim3(256), 0, (hipStream_t)stream, p, q, (T16*)dst));
+  with_elem(dst_dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(clip_preprocess_color_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, p, q, (T*)dst);
+  });
   return check_launch("clip_preprocess_color");
 }
 
@@ -437,10 +437,10 @@ extern "C" int vlfb_clip_preprocess(const vlfb_clip_desc* d, const uint8_t* fram
   p.to_rgb = d->to_rgb; p.wl = d->w_left; p.wtot = d->w_total; p.c_pad = d->c_pad;
   const long long total = (long long)p.T * p.crop_h * p.crop_w;
   const int grid = grid_for(total, 256);
-  if (dst_dtype == VLFB_F32)
-    hipLaunchKernelGGL(clip_preprocess_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, (float*)dst);
-  else
-    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_preprocess_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, (T16*)dst));
+  with_elem(dst_dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(clip_preprocess_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, (T*)dst);
+  });
   return check_launch("clip_preprocess");
 }
 
@@ -464,10 +464,9 @@ extern "C" int vlfb_clip_batch_preprocess(const vlfb_clip_item* items_host, cons
   if (rc != VLFB_OK) return rc;
   VLFB_REQUIRE(dst_dtype == VLFB_F32 || is16(dst_dtype), "clip_batch_preprocess: dst dtype must be f32 or bf16");
   const dim3 grid(tiles, frames, n_items), block(TILE_W, TILE_H);
-  if (dst_dtype == VLFB_F32)
-    hipLaunchKernelGGL(clip_batch_preprocess_kernel<float>, grid, block, 0, (hipStream_t)stream, items_dev);
-  else
-    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_batch_preprocess_kernel<T16>, grid, block, 0, (hipStream_t)stream, items_dev));
+  with_elem(dst_dtype, [&](auto t) {
+    hipLaunchKernelGGL(clip_batch_preprocess_kernel<decltype(t)>, grid, block, 0, (hipStream_t)stream, items_dev);
+  });
   return check_launch("clip_batch_preprocess");
 }
 
@@ -499,11 +498,8 @@ extern "C" int vlfb_clip_batch_preprocess_indexed(const vlfb_clip_item* items_ho
   if (rc != VLFB_OK) return rc;
   VLFB_REQUIRE(dst_dtype == VLFB_F32 || is16(dst_dtype), "%s: dst dtype must be f32 or bf16", what);
   const dim3 grid(tiles, frames, n_items), block(TILE_W, TILE_H);
-  if (dst_dtype == VLFB_F32)
-    hipLaunchKernelGGL(clip_batch_preprocess_indexed_kernel<float>, grid, block, 0, (hipStream_t)stream, items_dev, index_dev,
-                       index_stride);
-  else
-    VLFB_WITH_T16(dst_dtype, hipLaunchKernelGGL(clip_batch_preprocess_indexed_kernel<T16>, grid, block, 0, (hipStream_t)stream,
-                                                items_dev, index_dev, index_stride));
+  with_elem(dst_dtype, [&](auto t) {
+    hipLaunchKernelGGL(clip_batch_preprocess_indexed_kernel<decltype(t)>, grid, block, 0, (hipStream_t)stream, items_dev, index_dev, index_stride);
+  });
   return check_launch(what);
 }

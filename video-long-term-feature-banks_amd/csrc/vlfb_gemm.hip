@@ -753,100 +753,81 @@ __global__ void wgrad_bias_reduce_kernel(const float* __restrict__ ws_b, float* 
 
 // ---- host side: the launch of a plan (the planner is vlfb_conv_plan.hip) -------------------------
 // every instance declares the LDS it needs once (64 KiB for the 128x128 tile)
-template <typename K>
-void launch_k(K kernel, const Plan& pl, hipStream_t s) {
-  static bool configured = false;  // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, pl.grid, dim3(pl.threads), pl.lds, s, pl.gp);
+template <auto Kernel>
+int launch_k(const Plan& pl, hipStream_t s, const char* what) {
+  return launch_lds<Kernel, 80 * 1024>(pl.grid, dim3(pl.threads), pl.lds, s, what, pl.gp);
 }
 // one tile shape, with or without the uniform-tap gather (UT only exists for gathered, unpacked operands)
 template <typename T, typename OutT, int BM, int BN, bool IDENT, bool DGRAD, bool PACKW, int RB, bool PRE, int NW>
-void launch_nt_shape(const Plan& pl, hipStream_t s) {
+int launch_nt_shape(const Plan& pl, hipStream_t s, const char* what) {
   if constexpr (!IDENT && !PACKW) {
     if constexpr (DGRAD && sizeof(T) == 2) {
-      if (pl.w2i) {
-        launch_k(gemm_nt_kernel<T, OutT, BM, BN, IDENT, DGRAD, PACKW, RB, PRE, NW, 2, true, false, true>, pl, s);
-        return;
-      }
+      if (pl.w2i) return launch_k<gemm_nt_kernel<T, OutT, BM, BN, IDENT, DGRAD, PACKW, RB, PRE, NW, 2, true, false, true>>(pl, s, what);
     }
-    if (pl.ut) {
-      launch_k(gemm_nt_kernel<T, OutT, BM, BN, IDENT, DGRAD, PACKW, RB, PRE, NW, 2, true>, pl, s);
-      return;
-    }
+    if (pl.ut) return launch_k<gemm_nt_kernel<T, OutT, BM, BN, IDENT, DGRAD, PACKW, RB, PRE, NW, 2, true>>(pl, s, what);
   }
-  launch_k(gemm_nt_kernel<T, OutT, BM, BN, IDENT, DGRAD, PACKW, RB, PRE, NW, 2, false>, pl, s);
+  return launch_k<gemm_nt_kernel<T, OutT, BM, BN, IDENT, DGRAD, PACKW, RB, PRE, NW, 2, false>>(pl, s, what);
 }
 
 template <typename T, typename OutT, bool IDENT, bool DGRAD, bool PACKW>
-void launch_nt(const Plan& pl, hipStream_t s) {
+int launch_nt(const Plan& pl, hipStream_t s, const char* what) {
   constexpr bool BF = sizeof(T) == 2;
   constexpr bool CAN_PRE = BF && sizeof(OutT) == 2 && !PACKW;
   constexpr int NW = BF ? 8 : 4;        // bf16: 8 waves (2 x 4) per workgroup; fp32 parity path: 4 (2 x 2)
   if (pl.bn == 64) {
-    if (CAN_PRE && pl.pre) launch_nt_shape<T, OutT, 128, 64, IDENT, DGRAD, PACKW, 128, CAN_PRE, NW>(pl, s);
-    else launch_nt_shape<T, OutT, 128, 64, IDENT, DGRAD, PACKW, 128, false, NW>(pl, s);
-    return;
+    if (CAN_PRE && pl.pre) return launch_nt_shape<T, OutT, 128, 64, IDENT, DGRAD, PACKW, 128, CAN_PRE, NW>(pl, s, what);
+    return launch_nt_shape<T, OutT, 128, 64, IDENT, DGRAD, PACKW, 128, false, NW>(pl, s, what);
   }
-  if (CAN_PRE && pl.pre) launch_nt_shape<T, OutT, 128, 128, IDENT, DGRAD, PACKW, 128, CAN_PRE, NW>(pl, s);
-  else launch_nt_shape<T, OutT, 128, 128, IDENT, DGRAD, PACKW, 128, false, NW>(pl, s);
+  if (CAN_PRE && pl.pre) return launch_nt_shape<T, OutT, 128, 128, IDENT, DGRAD, PACKW, 128, CAN_PRE, NW>(pl, s, what);
+  return launch_nt_shape<T, OutT, 128, 128, IDENT, DGRAD, PACKW, 128, false, NW>(pl, s, what);
 }
 template <typename T, typename OutT, bool IDENT, bool PACKW>
-void launch_tn(const Plan& pl, hipStream_t s) {
-  if (pl.bm == 128 && pl.bn == 128) launch_k(gemm_tn_kernel<T, OutT, 128, 128, IDENT, PACKW>, pl, s);
-  else if (pl.bm == 64 && pl.bn == 256) launch_k(gemm_tn_kernel<T, OutT, 64, 256, IDENT, PACKW>, pl, s);
-  else if (pl.bm == 64 && pl.bn == 128) launch_k(gemm_tn_kernel<T, OutT, 64, 128, IDENT, PACKW>, pl, s);
-  else if (pl.bm == 128 && pl.bn == 64) launch_k(gemm_tn_kernel<T, OutT, 128, 64, IDENT, PACKW>, pl, s);
-  else launch_k(gemm_tn_kernel<T, OutT, 64, 64, IDENT, PACKW>, pl, s);
+int launch_tn(const Plan& pl, hipStream_t s, const char* what) {
+  if (pl.bm == 128 && pl.bn == 128) return launch_k<gemm_tn_kernel<T, OutT, 128, 128, IDENT, PACKW>>(pl, s, what);
+  if (pl.bm == 64 && pl.bn == 256) return launch_k<gemm_tn_kernel<T, OutT, 64, 256, IDENT, PACKW>>(pl, s, what);
+  if (pl.bm == 64 && pl.bn == 128) return launch_k<gemm_tn_kernel<T, OutT, 64, 128, IDENT, PACKW>>(pl, s, what);
+  if (pl.bm == 128 && pl.bn == 64) return launch_k<gemm_tn_kernel<T, OutT, 128, 64, IDENT, PACKW>>(pl, s, what);
+  return launch_k<gemm_tn_kernel<T, OutT, 64, 64, IDENT, PACKW>>(pl, s, what);
 }
 
-template <typename T, typename OutT, bool IDENT, bool PACKW, bool SP = false>
-void launch_tn_tr(const Plan& pl, hipStream_t s) {
-  if (pl.bm == 128 && pl.bn == 128) launch_k(gemm_tn_tr_kernel<T, OutT, 128, 128, IDENT, PACKW, 8, SP>, pl, s);   // 8 waves
-  else if (pl.bm == 64 && pl.bn == 128) launch_k(gemm_tn_tr_kernel<T, OutT, 64, 128, IDENT, PACKW, 4, SP>, pl, s);
-  else if (pl.bm == 128 && pl.bn == 64) launch_k(gemm_tn_tr_kernel<T, OutT, 128, 64, IDENT, PACKW, 4, SP>, pl, s);
-  else launch_k(gemm_tn_tr_kernel<T, OutT, 64, 64, IDENT, PACKW, 4, SP>, pl, s);
+template <typename T, typename OutT, bool IDENT, bool PACKW, bool SP>
+int launch_tn_tr_as(const Plan& pl, hipStream_t s, const char* what) {
+  if (pl.bm == 128 && pl.bn == 128) return launch_k<gemm_tn_tr_kernel<T, OutT, 128, 128, IDENT, PACKW, 8, SP>>(pl, s, what);   // 8 waves
+  if (pl.bm == 64 && pl.bn == 128) return launch_k<gemm_tn_tr_kernel<T, OutT, 64, 128, IDENT, PACKW, 4, SP>>(pl, s, what);
+  if (pl.bm == 128 && pl.bn == 64) return launch_k<gemm_tn_tr_kernel<T, OutT, 128, 64, IDENT, PACKW, 4, SP>>(pl, s, what);
+  return launch_k<gemm_tn_tr_kernel<T, OutT, 64, 64, IDENT, PACKW, 4, SP>>(pl, s, what);
+}
+template <typename T, typename OutT, bool SP = false>
+int launch_tn_tr(const Plan& pl, hipStream_t s, const char* what) {
+  return pl.ident ? launch_tn_tr_as<T, OutT, true, false, SP>(pl, s, what)
+         : pl.packw ? launch_tn_tr_as<T, OutT, false, true, SP>(pl, s, what)
+                    : launch_tn_tr_as<T, OutT, false, false, SP>(pl, s, what);
 }
 
 template <typename T>
 int launch_stem_wgrad(const Plan& pl, hipStream_t s) {
-  static bool configured = false;     // per element type (template instance)
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(stem_wgrad_kernel<T>, pl.grid, dim3(512), pl.lds, s, pl.gp);
-  return check_launch("conv wgrad (stem) kernel");
+  return launch_lds<stem_wgrad_kernel<T>, 160 * 1024>(pl.grid, dim3(512), pl.lds, s, "conv wgrad (stem) kernel", pl.gp);
 }
 
 // the tiled families (tn, tn_tr, nt) in the instance of the element types
 template <typename T, typename OutT>
 int launch_tiled(const vlfb_conv_desc* d, const Plan& pl, hipStream_t s) {
   if constexpr (sizeof(T) == 2) {
-    if (pl.family == Family::tn_tr) {
-      if (pl.ident) launch_tn_tr<T, OutT, true, false>(pl, s);
-      else if (pl.packw) launch_tn_tr<T, OutT, false, true>(pl, s);
-      else launch_tn_tr<T, OutT, false, false>(pl, s);
-      return check_launch("conv wgrad (tr) kernel");
-    }
+    if (pl.family == Family::tn_tr) return launch_tn_tr<T, OutT>(pl, s, "conv wgrad (tr) kernel");
   }
+  const char* what = "conv kernel";
   if (d->mode == VLFB_CONV_WGRAD) {
-    if (pl.ident) launch_tn<T, OutT, true, false>(pl, s);
-    else if (pl.packw) launch_tn<T, OutT, false, true>(pl, s);
-    else launch_tn<T, OutT, false, false>(pl, s);
-  } else if (d->mode == VLFB_CONV_DGRAD) {
-    if (pl.ident) launch_nt<T, OutT, true, false, false>(pl, s);
-    else launch_nt<T, OutT, false, true, false>(pl, s);
-  } else {
-    if (pl.ident) launch_nt<T, OutT, true, false, false>(pl, s);
-    else if (pl.packw) launch_nt<T, OutT, false, false, true>(pl, s);
-    else launch_nt<T, OutT, false, false, false>(pl, s);
+    if (pl.ident) return launch_tn<T, OutT, true, false>(pl, s, what);
+    if (pl.packw) return launch_tn<T, OutT, false, true>(pl, s, what);
+    return launch_tn<T, OutT, false, false>(pl, s, what);
   }
-  return check_launch("conv kernel");
+  if (d->mode == VLFB_CONV_DGRAD) {
+    if (pl.ident) return launch_nt<T, OutT, true, false, false>(pl, s, what);
+    return launch_nt<T, OutT, false, true, false>(pl, s, what);
+  }
+  if (pl.ident) return launch_nt<T, OutT, true, false, false>(pl, s, what);
+  if (pl.packw) return launch_nt<T, OutT, false, false, true>(pl, s, what);
+  return launch_nt<T, OutT, false, false, false>(pl, s, what);
 }
 
 // the kernel of the plan's family
@@ -865,11 +846,7 @@ int launch_plan(const vlfb_conv_desc* d, const Plan& pl, hipStream_t s) {
     case Family::wgrad_rows: return launch_wgrad_rows(g, pl.splits, pl.lds, d->dtype, s);
     case Family::wgrad_rows_fat: return launch_wgrad_rows_fat(g, pl.splits, d->dtype, s);
     case Family::tn_split: return launch_tn_split(g, pl.bm, pl.bn, pl.ident, pl.packw, pl.grid, pl.lds, s);
-    case Family::tn_tr_planes:
-      if (pl.ident) launch_tn_tr<bf16_t, float, true, false, true>(pl, s);
-      else if (pl.packw) launch_tn_tr<bf16_t, float, false, true, true>(pl, s);
-      else launch_tn_tr<bf16_t, float, false, false, true>(pl, s);
-      return check_launch("conv wgrad (planes) kernel");
+    case Family::tn_tr_planes: return launch_tn_tr<bf16_t, float, true>(pl, s, "conv wgrad (planes) kernel");
     case Family::nt8:
       return launch_nt8(g, pl.bm, pl.bn, pl.nt8_mode, d->dtype, out_f32, (unsigned)(d->batch > 0 ? d->batch : 1), s);
     case Family::nt_stream: return launch_nts(g, pl.nts_mode, d->dtype, s);
@@ -1044,13 +1021,10 @@ static int conv_run_impl(const vlfb_conv_desc* d, const void* A, const void* B, 
                        rowscale, n, g.ldo, pl.splits, d->alpha, d->accumulate, bias_rows, bias_rows ? dbias : nullptr,  \
                        (int)d->Cn, (int)wblocks);                                                                       \
   } while (0)
-    if (d->out_dtype == VLFB_F32) {
-      if (G == 16) VLFB_REDUCE(float, 16, 16); else if (G == 4) VLFB_REDUCE(float, 4, 64); else VLFB_REDUCE(float, 1, 64);
-    } else if (d->out_dtype == VLFB_F16) {
-      if (G == 16) VLFB_REDUCE(f16_t, 16, 16); else if (G == 4) VLFB_REDUCE(f16_t, 4, 64); else VLFB_REDUCE(f16_t, 1, 64);
-    } else {
-      if (G == 16) VLFB_REDUCE(bf16_t, 16, 16); else if (G == 4) VLFB_REDUCE(bf16_t, 4, 64); else VLFB_REDUCE(bf16_t, 1, 64);
-    }
+    with_elem(d->out_dtype, [&](auto t) {         // (the plan holds one of the three element types)
+      using OT = decltype(t);
+      if (G == 16) VLFB_REDUCE(OT, 16, 16); else if (G == 4) VLFB_REDUCE(OT, 4, 64); else VLFB_REDUCE(OT, 1, 64);
+    });
 #undef VLFB_REDUCE
     return check_launch("wgrad reduce");
   }

@@ -216,59 +216,44 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const GP p) {
   }
 }
 
-template <typename K>
-void launch8(K kernel, const GP& gp, dim3 grid, size_t lds, hipStream_t s) {
-  static bool configured = false;   // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, grid, dim3(512), lds, s, gp);
+constexpr const char* kWhatNt8 = "conv kernel (256-row pipelined)";
+template <auto Kernel>
+int launch8(const GP& gp, dim3 grid, size_t lds, hipStream_t s, const char* what) {
+  return launch_lds<Kernel, 160 * 1024>(grid, dim3(512), lds, s, what, gp);
 }
 
 template <typename T, typename OutT, int BN, int RV>
-void launch_nt8_bn(const GP& gp, int mode, dim3 grid, hipStream_t s) {
+int launch_nt8_bn(const GP& gp, int mode, dim3 grid, hipStream_t s) {
   constexpr size_t lds = (BN == 256 ? 2 : 3) * (size_t)(2 + BN / 128) * 16384;
   const bool ktail = (gp.K & 63) != 0;
   if (mode == 0) {
-    if (ktail) launch8(gemm_nt8_kernel<T, OutT, BN, 0, true, RV>, gp, grid, lds, s);
-    else launch8(gemm_nt8_kernel<T, OutT, BN, 0, false, RV>, gp, grid, lds, s);
-  } else if (mode == 1) {
-    launch8(gemm_nt8_kernel<T, OutT, BN, 1, false, RV>, gp, grid, lds, s);
-  } else {
-    launch8(gemm_nt8_kernel<T, OutT, BN, 2, false, RV>, gp, grid, lds, s);
+    if (ktail) return launch8<gemm_nt8_kernel<T, OutT, BN, 0, true, RV>>(gp, grid, lds, s, kWhatNt8);
+    return launch8<gemm_nt8_kernel<T, OutT, BN, 0, false, RV>>(gp, grid, lds, s, kWhatNt8);
   }
+  if (mode == 1) return launch8<gemm_nt8_kernel<T, OutT, BN, 1, false, RV>>(gp, grid, lds, s, kWhatNt8);
+  return launch8<gemm_nt8_kernel<T, OutT, BN, 2, false, RV>>(gp, grid, lds, s, kWhatNt8);
 }
 template <typename T, typename OutT>
-void launch_nt8_t(const GP& gp, int mode, int bm, int bn, dim3 grid, hipStream_t s) {
-  if (bn == 256) {
-    if (bm == 196) launch_nt8_bn<T, OutT, 256, 98>(gp, mode, grid, s); else launch_nt8_bn<T, OutT, 256, 128>(gp, mode, grid, s);
-  } else {
-    if (bm == 196) launch_nt8_bn<T, OutT, 128, 98>(gp, mode, grid, s); else launch_nt8_bn<T, OutT, 128, 128>(gp, mode, grid, s);
-  }
+int launch_nt8_t(const GP& gp, int mode, int bm, int bn, dim3 grid, hipStream_t s) {
+  if (bn == 256) return bm == 196 ? launch_nt8_bn<T, OutT, 256, 98>(gp, mode, grid, s) : launch_nt8_bn<T, OutT, 256, 128>(gp, mode, grid, s);
+  return bm == 196 ? launch_nt8_bn<T, OutT, 128, 98>(gp, mode, grid, s) : launch_nt8_bn<T, OutT, 128, 128>(gp, mode, grid, s);
 }
 
 }  // namespace
 
 int launch_nt8(const GP& gp, int bm, int bn, int mode, int dtype, bool out_f32, unsigned batch, hipStream_t s) {
   const dim3 grid((unsigned)(gp.tiles_m * gp.tiles_n), 1, batch);
-  if (dtype == VLFB_F16) {
-    if (out_f32) launch_nt8_t<f16_t, float>(gp, mode, bm, bn, grid, s); else launch_nt8_t<f16_t, f16_t>(gp, mode, bm, bn, grid, s);
-  } else {
-    if (out_f32) launch_nt8_t<bf16_t, float>(gp, mode, bm, bn, grid, s); else launch_nt8_t<bf16_t, bf16_t>(gp, mode, bm, bn, grid, s);
-  }
-  return check_launch("conv kernel (256-row pipelined)");
+  int rc;
+  VLFB_WITH_T16(dtype, rc = out_f32 ? launch_nt8_t<T16, float>(gp, mode, bm, bn, grid, s) : launch_nt8_t<T16, T16>(gp, mode, bm, bn, grid, s));
+  return rc;
 }
 
 int launch_tn8(const GP& gp, dim3 grid, int dtype, bool out_f32, hipStream_t s) {
   constexpr size_t lds = 2 * 4 * 16384;
-  if (dtype == VLFB_F16) {
-    if (out_f32) launch8(gemm_tn8_kernel<f16_t, float>, gp, grid, lds, s); else launch8(gemm_tn8_kernel<f16_t, f16_t>, gp, grid, lds, s);
-  } else {
-    if (out_f32) launch8(gemm_tn8_kernel<bf16_t, float>, gp, grid, lds, s); else launch8(gemm_tn8_kernel<bf16_t, bf16_t>, gp, grid, lds, s);
-  }
-  return check_launch("conv wgrad kernel (256x256 pipelined)");
+  const char* what = "conv wgrad kernel (256x256 pipelined)";
+  int rc;
+  VLFB_WITH_T16(dtype, rc = out_f32 ? launch8<gemm_tn8_kernel<T16, float>>(gp, grid, lds, s, what) : launch8<gemm_tn8_kernel<T16, T16>>(gp, grid, lds, s, what));
+  return rc;
 }
 
 }  // namespace vlfb

@@ -297,28 +297,21 @@ __global__ __launch_bounds__(NW * 64) void gemm_nts_kernel(const GP p, const int
   }
 }
 
-template <typename K>
-int launch_s(K kernel, const GP& gp, int dgrad, int lgN, unsigned nwg, int nw, size_t lds, hipStream_t s) {
-  static bool configured = false;   // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(nw * 64), lds, s, gp, dgrad, lgN);
-  return check_launch("conv kernel (weight-resident streaming)");
+template <auto Kernel>
+int launch_s(const GP& gp, int dgrad, int lgN, unsigned nwg, int nw, size_t lds, hipStream_t s) {
+  return launch_lds<Kernel, 160 * 1024>(dim3(nwg), dim3(nw * 64), lds, s, "conv kernel (weight-resident streaming)", gp, dgrad, lgN);
 }
 
 template <typename T, int NF, int MF, int NW>
 int launch_nts_shape(const GP& gp, int mode, int uk, int lgN, unsigned nwg, size_t lds, hipStream_t s) {
   const int dgrad = mode == 2;
   if (mode == 0) {
-    if (uk == 1) return launch_s(gemm_nts_kernel<T, NF, MF, 1, false, NW>, gp, 0, lgN, nwg, NW, lds, s);
-    if (uk == 2) return launch_s(gemm_nts_kernel<T, NF, MF, 2, false, NW>, gp, 0, lgN, nwg, NW, lds, s);
-    return launch_s(gemm_nts_kernel<T, NF, MF, 4, false, NW>, gp, 0, lgN, nwg, NW, lds, s);
+    if (uk == 1) return launch_s<gemm_nts_kernel<T, NF, MF, 1, false, NW>>(gp, 0, lgN, nwg, NW, lds, s);
+    if (uk == 2) return launch_s<gemm_nts_kernel<T, NF, MF, 2, false, NW>>(gp, 0, lgN, nwg, NW, lds, s);
+    return launch_s<gemm_nts_kernel<T, NF, MF, 4, false, NW>>(gp, 0, lgN, nwg, NW, lds, s);
   }
-  if (uk == 3) return launch_s(gemm_nts_kernel<T, NF, MF, 3, true, NW>, gp, dgrad, lgN, nwg, NW, lds, s);
-  return launch_s(gemm_nts_kernel<T, NF, MF, 4, true, NW>, gp, dgrad, lgN, nwg, NW, lds, s);
+  if (uk == 3) return launch_s<gemm_nts_kernel<T, NF, MF, 3, true, NW>>(gp, dgrad, lgN, nwg, NW, lds, s);
+  return launch_s<gemm_nts_kernel<T, NF, MF, 4, true, NW>>(gp, dgrad, lgN, nwg, NW, lds, s);
 }
 
 template <typename T>
@@ -338,13 +331,7 @@ int nts_chunk(int mode, long long K) {
 }
 
 int launch_nts(const GP& gp, int mode, int dtype, hipStream_t s) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    ncu = n / 8 * 8;
-  }
+  const int ncu = device_cus8();
   const int uk = nts_chunk(mode, gp.K);
   int lgN = 0;
   while ((1 << lgN) < gp.Ncols) ++lgN;

@@ -845,31 +845,25 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_sp_kernel(const GP p) {
   }
 }
 
-template <typename K>
-int launch_sp(K kernel, dim3 grid, size_t lds, const GP& gp, hipStream_t s, int threads = 256) {
-  static bool configured = false;     // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, gp);
-  return check_launch("split-bf16 conv kernel");
+template <auto Kernel>
+int launch_sp(dim3 grid, size_t lds, const GP& gp, hipStream_t s, int threads = 256) {
+  return launch_lds<Kernel, 128 * 1024>(grid, dim3(threads), lds, s, "split-bf16 conv kernel", gp);
 }
 
 template <int NPL, int BN, int NWN>
 int launch_nt_sp_waves(const GP& gp, int kind, bool ut, dim3 grid, size_t lds, hipStream_t s) {
   switch (kind) {
-    case 0: return launch_sp(gemm_nt_sp_kernel<NPL, BN, true, false, false, false, false, NWN>, grid, lds, gp, s);
-    case 1: return ut ? launch_sp(gemm_nt_sp_kernel<NPL, BN, false, false, false, true, false, NWN>, grid, lds, gp, s)
-                      : launch_sp(gemm_nt_sp_kernel<NPL, BN, false, false, false, false, false, NWN>, grid, lds, gp, s);
+    case 0: return launch_sp<gemm_nt_sp_kernel<NPL, BN, true, false, false, false, false, NWN>>(grid, lds, gp, s);
+    case 1: return ut ? launch_sp<gemm_nt_sp_kernel<NPL, BN, false, false, false, true, false, NWN>>(grid, lds, gp, s)
+                      : launch_sp<gemm_nt_sp_kernel<NPL, BN, false, false, false, false, false, NWN>>(grid, lds, gp, s);
     case 2:
       if constexpr (NPL == 2) {
-        if (gp.s2) return launch_sp(gemm_nt_sp_kernel<NPL, BN, false, true, false, true, true, NWN>, grid, lds, gp, s);
+        if (gp.s2) return launch_sp<gemm_nt_sp_kernel<NPL, BN, false, true, false, true, true, NWN>>(grid, lds, gp, s);
       }
       if (gp.s2) return set_error(VLFB_ERR_UNSUPPORTED, "conv: class-major strided DGRAD exists for three-term products only");
-      return ut ? launch_sp(gemm_nt_sp_kernel<NPL, BN, false, true, false, true, false, NWN>, grid, lds, gp, s)
-                : launch_sp(gemm_nt_sp_kernel<NPL, BN, false, true, false, false, false, NWN>, grid, lds, gp, s);
-    default: return launch_sp(gemm_nt_sp_kernel<NPL, BN, false, false, true, false, false, NWN>, grid, lds, gp, s);
+      return ut ? launch_sp<gemm_nt_sp_kernel<NPL, BN, false, true, false, true, false, NWN>>(grid, lds, gp, s)
+                : launch_sp<gemm_nt_sp_kernel<NPL, BN, false, true, false, false, false, NWN>>(grid, lds, gp, s);
+    default: return launch_sp<gemm_nt_sp_kernel<NPL, BN, false, false, true, false, false, NWN>>(grid, lds, gp, s);
   }
 }
 template <int NPL, int BN>
@@ -931,9 +925,9 @@ int launch_nt_split(const GP& gp, int npl, int bn, int kind, bool ut, dim3 grid,
 
 template <int NPL, int BN>
 int launch_nt_pl_shape(const GP& gp, int kind, dim3 grid, size_t lds, hipStream_t s) {
-  if (kind == 0) return launch_sp(gemm_nt_pl_kernel<NPL, BN, true, false>, grid, lds, gp, s);
-  if (kind == 1) return launch_sp(gemm_nt_pl_kernel<NPL, BN, false, false>, grid, lds, gp, s);
-  return launch_sp(gemm_nt_pl_kernel<NPL, BN, false, true>, grid, lds, gp, s);
+  if (kind == 0) return launch_sp<gemm_nt_pl_kernel<NPL, BN, true, false>>(grid, lds, gp, s);
+  if (kind == 1) return launch_sp<gemm_nt_pl_kernel<NPL, BN, false, false>>(grid, lds, gp, s);
+  return launch_sp<gemm_nt_pl_kernel<NPL, BN, false, true>>(grid, lds, gp, s);
 }
 
 int launch_nt_planes(const GP& gp, int npl, int bn, int kind, dim3 grid, size_t lds, hipStream_t s) {
@@ -947,9 +941,9 @@ int launch_tn_split(const GP& gp, int bp, int bq, bool ident, bool packw, dim3 g
   do {                                                                                                         \
     constexpr int NW8 = ((BP) >= 128 && (BQ) >= 128) ? 8 : 4;  /* (64-row tiles measured slower with 8 waves ...) */                                                                  \
     constexpr int NWS = (BQ) >= 128 ? 8 : 4;                   /* (... except the packed stem: 3.55 -> 2.8 ms) */  \
-    if (ident) return launch_sp(gemm_tn_sp_kernel<BP, BQ, true, false, NW8>, grid, lds, gp, s, 64 * NW8);      \
-    if (packw) return launch_sp(gemm_tn_sp_kernel<BP, BQ, false, true, NWS>, grid, lds, gp, s, 64 * NWS);      \
-    return launch_sp(gemm_tn_sp_kernel<BP, BQ, false, false, NW8>, grid, lds, gp, s, 64 * NW8);                \
+    if (ident) return launch_sp<gemm_tn_sp_kernel<BP, BQ, true, false, NW8>>(grid, lds, gp, s, 64 * NW8);      \
+    if (packw) return launch_sp<gemm_tn_sp_kernel<BP, BQ, false, true, NWS>>(grid, lds, gp, s, 64 * NWS);      \
+    return launch_sp<gemm_tn_sp_kernel<BP, BQ, false, false, NW8>>(grid, lds, gp, s, 64 * NW8);                \
   } while (0)
   if (bp == 128 && bq == 128) VLFB_TN_SP(128, 128);
   if (bp == 64 && bq == 128) VLFB_TN_SP(64, 128);

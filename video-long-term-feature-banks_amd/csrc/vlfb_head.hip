@@ -481,22 +481,16 @@ __global__ void scale_kernel(float* x, long long n, float s) {
 
 using namespace vlfb;
 
-#define DISPATCH_T(dtype, NAME, ...)                                             \
-  if ((dtype) == VLFB_F32) { NAME<float> __VA_ARGS__; }                          \
-  else if ((dtype) == VLFB_BF16) { NAME<bf16_t> __VA_ARGS__; }                   \
-  else if ((dtype) == VLFB_F16) { NAME<f16_t> __VA_ARGS__; }                     \
-  else return set_error(VLFB_ERR_ARG, "bad dtype %d", (int)(dtype));
-
 extern "C" int vlfb_layernorm_fwd(const void* x, void* y, float* rstd, int dtype, int64_t rows,
                                   int64_t cols, float eps, vlfb_stream_t stream) {
   VLFB_REQUIRE(x && y && rstd && rows > 0 && cols > 0, "layernorm_fwd: bad args");
   int grid = grid_for(rows * 64, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, rstd, (long long)rows, (int)cols, eps);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(layernorm_fwd_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)x, (T16*)y, rstd, (long long)rows, (int)cols, eps));
-  else return set_error(VLFB_ERR_ARG, "layernorm_fwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, (T*)y, rstd, (long long)rows, (int)cols, eps);
+      }))
+    return set_error(VLFB_ERR_ARG, "layernorm_fwd: bad dtype");
   return check_launch("layernorm_fwd");
 }
 extern "C" int vlfb_layernorm_bwd(const void* dy, const void* y, const float* rstd, void* dx,
@@ -504,11 +498,11 @@ extern "C" int vlfb_layernorm_bwd(const void* dy, const void* y, const float* rs
   VLFB_REQUIRE(dy && y && rstd && dx && rows > 0 && cols > 0, "layernorm_bwd: bad args");
   int grid = grid_for(rows * 64, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(layernorm_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dy, (const float*)y, rstd, (float*)dx, (long long)rows, (int)cols);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(layernorm_bwd_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)dy, (const T16*)y, rstd, (T16*)dx, (long long)rows, (int)cols));
-  else return set_error(VLFB_ERR_ARG, "layernorm_bwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)dy, (const T*)y, rstd, (T*)dx, (long long)rows, (int)cols);
+      }))
+    return set_error(VLFB_ERR_ARG, "layernorm_bwd: bad dtype");
   return check_launch("layernorm_bwd");
 }
 static int dropout_fwd_any(const void* x, void* y, uint8_t* mask, int dtype, int64_t rows, int64_t inner,
@@ -519,11 +513,11 @@ static int dropout_fwd_any(const void* x, void* y, uint8_t* mask, int dtype, int
   int grid = grid_for(rows * inner * ch, 256);
   hipStream_t s = (hipStream_t)stream;
   const unsigned long long* sd = (const unsigned long long*)seed_dev;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(dropout_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, mask, (long long)rows, (long long)inner, (long long)ch, ratio, (unsigned long long)seed, sd);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(dropout_fwd_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)x, (T16*)y, mask, (long long)rows, (long long)inner, (long long)ch, ratio, (unsigned long long)seed, sd));
-  else return set_error(VLFB_ERR_ARG, "dropout_fwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dropout_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, (T*)y, mask, (long long)rows, (long long)inner, (long long)ch, ratio, (unsigned long long)seed, sd);
+      }))
+    return set_error(VLFB_ERR_ARG, "dropout_fwd: bad dtype");
   return check_launch("dropout_fwd");
 }
 extern "C" int vlfb_dropout_fwd(const void* x, void* y, uint8_t* mask, int dtype, int64_t rows,
@@ -542,11 +536,11 @@ extern "C" int vlfb_dropout_bwd(const void* dy, const uint8_t* mask, void* dx, i
   VLFB_REQUIRE(dy && mask && dx && n > 0, "dropout_bwd: bad args");
   int grid = grid_for(n, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(dropout_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)dy, mask, (float*)dx, (long long)n, ratio);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(dropout_bwd_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)dy, mask, (T16*)dx, (long long)n, ratio));
-  else return set_error(VLFB_ERR_ARG, "dropout_bwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dropout_bwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)dy, mask, (T*)dx, (long long)n, ratio);
+      }))
+    return set_error(VLFB_ERR_ARG, "dropout_bwd: bad dtype");
   return check_launch("dropout_bwd");
 }
 
@@ -555,11 +549,11 @@ extern "C" int vlfb_fc_fwd(const void* x, int dtype, const float* w, const float
   VLFB_REQUIRE(x && w && logits && rows > 0 && cin > 0 && cout > 0, "fc_fwd: bad args");
   int grid = grid_for(rows * cout * 64, 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(fc_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, w, b, logits, (long long)rows, (int)cin, (int)cout);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(fc_fwd_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)x, w, b, logits, (long long)rows, (int)cin, (int)cout));
-  else return set_error(VLFB_ERR_ARG, "fc_fwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(fc_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, w, b, logits, (long long)rows, (int)cin, (int)cout);
+      }))
+    return set_error(VLFB_ERR_ARG, "fc_fwd: bad dtype");
   return check_launch("fc_fwd");
 }
 extern "C" int vlfb_fc_bwd(const void* x, int dtype, const float* w, const float* dlogits, void* dx,
@@ -568,20 +562,16 @@ extern "C" int vlfb_fc_bwd(const void* x, int dtype, const float* w, const float
   VLFB_REQUIRE(x && w && dlogits && rows > 0 && cin > 0 && cout > 0, "fc_bwd: bad args");
   hipStream_t s = (hipStream_t)stream;
   if (!dtype_ok(dtype)) return set_error(VLFB_ERR_ARG, "fc_bwd: bad dtype");
-  if (dx) {
-    int grid = grid_for(rows * cin, 256);
-    if (dtype == VLFB_F32)
-      hipLaunchKernelGGL(fc_bwd_dx_kernel<float>, dim3(grid), dim3(256), 0, s, w, dlogits, (float*)dx, (long long)rows, (int)cin, (int)cout);
-    else
-      VLFB_WITH_T16(dtype, hipLaunchKernelGGL(fc_bwd_dx_kernel<T16>, dim3(grid), dim3(256), 0, s, w, dlogits, (T16*)dx, (long long)rows, (int)cin, (int)cout));
-  }
-  if (dw) {
-    int grid = grid_for(cout * cin, 256);
-    if (dtype == VLFB_F32)
-      hipLaunchKernelGGL(fc_bwd_dw_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, dlogits, dw, db, (long long)rows, (int)cin, (int)cout, accumulate);
-    else
-      VLFB_WITH_T16(dtype, hipLaunchKernelGGL(fc_bwd_dw_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)x, dlogits, dw, db, (long long)rows, (int)cin, (int)cout, accumulate));
-  }
+  if (dx)
+    with_elem(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(fc_bwd_dx_kernel<T>, dim3(grid_for(rows * cin, 256)), dim3(256), 0, s, w, dlogits, (T*)dx, (long long)rows, (int)cin, (int)cout);
+    });
+  if (dw)
+    with_elem(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(fc_bwd_dw_kernel<T>, dim3(grid_for(cout * cin, 256)), dim3(256), 0, s, (const T*)x, dlogits, dw, db, (long long)rows, (int)cin, (int)cout, accumulate);
+    });
   return check_launch("fc_bwd");
 }
 extern "C" int vlfb_sigmoid_ce(const float* logits, const int32_t* labels, float* prob, float* loss,

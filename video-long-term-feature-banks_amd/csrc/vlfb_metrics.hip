@@ -280,11 +280,10 @@ extern "C" int vlfb_topk_hits(const void* scores, int dtype, const int32_t* labe
   if (rows == 0) return VLFB_OK;
   VLFB_REQUIRE(scores != nullptr && labels != nullptr, "topk_hits: scores and labels are required");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == VLFB_F32)
-    topk_hits_kernel<float><<<1, TOPK_WAVES * 64, 0, s>>>(static_cast<const float*>(scores), labels, (int)rows, (int)cols, tk, hits);
-  else
-    VLFB_WITH_T16(dtype, (topk_hits_kernel<T16><<<1, TOPK_WAVES * 64, 0, s>>>(static_cast<const T16*>(scores), labels, (int)rows,
-                                                                               (int)cols, tk, hits)));
+  with_elem(dtype, [&](auto t) {
+    using T = decltype(t);
+    topk_hits_kernel<T><<<1, TOPK_WAVES * 64, 0, s>>>(static_cast<const T*>(scores), labels, (int)rows, (int)cols, tk, hits);
+  });
   return check_launch("topk_hits");
 }
 
@@ -317,13 +316,11 @@ extern "C" int vlfb_scores_merge_max(const void* scores, int dtype, const int32_
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned grid = (unsigned)((cols + MERGE_THREADS - 1) / MERGE_THREADS);
   long long* cur = reinterpret_cast<long long*>(cursor);
-  if (dtype == VLFB_F32)
-    merge_max_kernel<float><<<grid, MERGE_THREADS, 0, s>>>(static_cast<const float*>(scores), labels, (int)rows, (int)cols, table,
-                                                          table_labels, n_items, total_rows, cur, mismatches);
-  else
-    VLFB_WITH_T16(dtype, (merge_max_kernel<T16><<<grid, MERGE_THREADS, 0, s>>>(static_cast<const T16*>(scores), labels, (int)rows,
-                                                                                (int)cols, table, table_labels, n_items, total_rows,
-                                                                                cur, mismatches)));
+  with_elem(dtype, [&](auto t) {
+    using T = decltype(t);
+    merge_max_kernel<T><<<grid, MERGE_THREADS, 0, s>>>(static_cast<const T*>(scores), labels, (int)rows, (int)cols, table, table_labels,
+                                                      n_items, total_rows, cur, mismatches);
+  });
   cursor_advance_kernel<<<1, 64, 0, s>>>(cur, (int)rows);
   return check_launch("scores_merge_max");
 }

@@ -129,7 +129,6 @@ __device__ __forceinline__ float rounded_mul(float a, float b) {
   asm volatile("" : "+v"(v));
   return v;
 }
-struct SplitW {};       // tag type: weight_prep kernels instantiated with it write planes instead of elements
 template <int NPL>
 __device__ __forceinline__ void store_terms(bf16_t* dst, long long idx, long long plane, float v) {
 #pragma unroll
@@ -139,84 +138,73 @@ __device__ __forceinline__ void store_terms(bf16_t* dst, long long idx, long lon
     v -= bf2f(t);
   }
 }
-template <typename T> struct WStore {
-  __device__ static __forceinline__ void fprop(void* base, long long idx, long long, float v) { Elem<T>::st(reinterpret_cast<T*>(base) + idx, v); }
-  __device__ static __forceinline__ void dgrad(void* base, long long idx, long long, float v) { Elem<T>::st(reinterpret_cast<T*>(base) + idx, v); }
-};
-template <> struct WStore<SplitW> {
-  __device__ static __forceinline__ void fprop(void* base, long long idx, long long plane, float v) { store_terms<3>(reinterpret_cast<bf16_t*>(base), idx, plane, v); }
-  __device__ static __forceinline__ void dgrad(void* base, long long idx, long long plane, float v) { store_terms<2>(reinterpret_cast<bf16_t*>(base), idx, plane, v); }
-};
-
-// "mix" engine (VLFB_MIX): split-bf16 forward, fp16 backward -- the FPROP copy as the three bf16 term planes of VLFB_SPLIT,
-// the DGRAD copy as plain fp16 elements [Cin][taps][Cout]
-struct MixW {};
-template <> struct WStore<MixW> {
-  __device__ static __forceinline__ void fprop(void* base, long long idx, long long plane, float v) { store_terms<3>(reinterpret_cast<bf16_t*>(base), idx, plane, v); }
-  __device__ static __forceinline__ void dgrad(void* base, long long idx, long long, float v) { reinterpret_cast<unsigned short*>(base)[idx] = f2h(v); }
-};
-
-// VLFB_MIX_W2: the DGRAD copy as TWO fp16 terms of (w * s) * VLFB_MIX_W2_SCALE, [Cin][term][taps][Cout] -- the weight of
-// a convolution with a doubled outermost tap dimension of dilation 0 (every tap is visited once per term), which the
-// plain fp16 DGRAD kernels contract with the fp16 gradient: dX = dY . (Wh + Wl), 22 significant bits of W
-struct MixW2 {};
-template <> struct WStore<MixW2> : WStore<MixW> {};
-
-// VLFB_MIXH / VLFB_MIXH_W2: the two-plane fp16 forward (VLFB_MATH_F16X3) -- the FPROP copy as the two fp16 terms of
-// (w * s) * VLFB_MIX_W2_SCALE, planes [term][Cout][taps][Cin] (the scale keeps the low term of a small weight in the fp16
-// normal range; the launch's alpha carries its inverse); the DGRAD copy as VLFB_MIX / VLFB_MIX_W2
-struct MixHW {};
-struct MixHW2 {};
-__device__ __forceinline__ void store_h2(void* base, long long idx, long long plane, float v) {
-  unsigned short* o = reinterpret_cast<unsigned short*>(base);
+// the two fp16 terms of v * VLFB_MIX_W2_SCALE, `stride` elements apart: h = fp16(sv), l = fp16(sv - h).  The scale keeps
+// the low term of a small weight in the fp16 normal range; the launch's alpha carries its inverse.
+__device__ __forceinline__ void store_scaled2(unsigned short* o, long long stride, float v) {
   const float sv = v * VLFB_MIX_W2_SCALE;
   const unsigned short h = f2h(sv);
-  o[idx] = h;
-  o[plane + idx] = f2h(sv - h2f(h));
+  o[0] = h;
+  o[stride] = f2h(sv - h2f(h));
 }
-template <> struct WStore<MixHW> {
-  __device__ static __forceinline__ void fprop(void* base, long long idx, long long plane, float v) { store_h2(base, idx, plane, v); }
-  __device__ static __forceinline__ void dgrad(void* base, long long idx, long long, float v) { reinterpret_cast<unsigned short*>(base)[idx] = f2h(v); }
+
+// ---- weight operand formats -------------------------------------------------------------------
+// A weight code of include/vlfb.h names a PAIR: the format of the FPROP copy and the format of the DGRAD copy
+// (with_weight_format below is the table).  Each format owns its addressing and its rounding; `plane` is
+// Cout * taps * Cin, the elements of one copy.
+//
+// FPROP copies, order [Cout][taps][Cin] (idx is the element's index in the fp32 master):
+template <typename T> struct WfElems {          // elements of T
+  __device__ static __forceinline__ void st(void* base, long long idx, long long, float v) { Elem<T>::st(reinterpret_cast<T*>(base) + idx, v); }
 };
-template <> struct WStore<MixHW2> : WStore<MixHW> {};
-// VLFB_MIX_W2I / VLFB_MIXH_W2I: the two-term DGRAD copy interleaved per 64-channel k-tile, [Cin][taps][Cout / 64][term][64]
-// (the weight operand of VLFB_MATH_F16W2: gemm_nt_kernel<.., W2I>)
-struct MixW2I {};
-struct MixHW2I {};
-template <> struct WStore<MixW2I> : WStore<MixW> {};
-template <> struct WStore<MixHW2I> : WStore<MixHW> {};
-
-template <typename T>
-__device__ __forceinline__ void wstore_dgrad(void* base, int ci, int tap, int co, int taps, int cout, long long plane, float v) {
-  if constexpr (std::is_same<T, MixW2>::value || std::is_same<T, MixHW2>::value) {
-    unsigned short* o = reinterpret_cast<unsigned short*>(base) + ((long long)ci * 2 * taps + tap) * cout + co;
-    const float sv = v * VLFB_MIX_W2_SCALE;
-    const unsigned short h = f2h(sv);
-    o[0] = h;
-    o[(long long)taps * cout] = f2h(sv - h2f(h));
-  } else if constexpr (std::is_same<T, MixW2I>::value || std::is_same<T, MixHW2I>::value) {
-    unsigned short* o = reinterpret_cast<unsigned short*>(base) + (((long long)ci * taps + tap) * cout + (co & ~63)) * 2 + (co & 63);
-    const float sv = v * VLFB_MIX_W2_SCALE;
-    const unsigned short h = f2h(sv);
-    o[0] = h;
-    o[64] = f2h(sv - h2f(h));
-  } else {
-    WStore<T>::dgrad(base, ((long long)ci * taps + tap) * cout + co, plane, v);
+struct WfTerms3 {                               // the three bf16 term planes of the split-bf16 forward, [term][...]
+  __device__ static __forceinline__ void st(void* base, long long idx, long long plane, float v) { store_terms<3>(reinterpret_cast<bf16_t*>(base), idx, plane, v); }
+};
+struct WfScaled2 {                              // the two-plane fp16 forward (VLFB_MATH_F16X3): two scaled fp16 planes, [term][...]
+  __device__ static __forceinline__ void st(void* base, long long idx, long long plane, float v) { store_scaled2(reinterpret_cast<unsigned short*>(base) + idx, plane, v); }
+};
+// DGRAD copies, order [Cin][taps][Cout]:
+template <typename T> struct WdElems {          // elements of T
+  static constexpr int kCoutMultiple = 1;
+  __device__ static __forceinline__ void st(void* base, int ci, int tap, int co, int taps, int cout, long long, float v) {
+    Elem<T>::st(reinterpret_cast<T*>(base) + ((long long)ci * taps + tap) * cout + co, v);
   }
-}
+};
+struct WdTerms2 {                               // two bf16 term planes, [term][...]
+  static constexpr int kCoutMultiple = 1;
+  __device__ static __forceinline__ void st(void* base, int ci, int tap, int co, int taps, int cout, long long plane, float v) {
+    store_terms<2>(reinterpret_cast<bf16_t*>(base), ((long long)ci * taps + tap) * cout + co, plane, v);
+  }
+};
+// two scaled fp16 terms as [Cin][term][taps][Cout] -- the weight of a convolution with a doubled outermost tap dimension
+// of dilation 0 (every tap is visited once per term), which the plain fp16 DGRAD kernels contract with the fp16 gradient:
+// dX = dY . (Wh + Wl), 22 significant bits of W
+struct WdScaled2 {
+  static constexpr int kCoutMultiple = 1;
+  __device__ static __forceinline__ void st(void* base, int ci, int tap, int co, int taps, int cout, long long, float v) {
+    store_scaled2(reinterpret_cast<unsigned short*>(base) + ((long long)ci * 2 * taps + tap) * cout + co, (long long)taps * cout, v);
+  }
+};
+// ... interleaved per 64-channel k-tile, [Cin][taps][Cout / 64][term][64] (the weight operand of VLFB_MATH_F16W2:
+// gemm_nt_kernel<.., W2I>)
+struct WdScaled2I {
+  static constexpr int kCoutMultiple = 64;
+  __device__ static __forceinline__ void st(void* base, int ci, int tap, int co, int taps, int cout, long long, float v) {
+    store_scaled2(reinterpret_cast<unsigned short*>(base) + (((long long)ci * taps + tap) * cout + (co & ~63)) * 2 + (co & 63), 64, v);
+  }
+};
 
-// w[Cout][taps][Cin] fp32 (+ scale[Cout]) -> fprop copy (same order) in T
-template <typename T>
+// w[Cout][taps][Cin] fp32 (+ scale[Cout]) -> fprop copy (same order) in the FPROP format F
+template <typename F>
 __global__ void weight_prep_fprop_kernel(const float* __restrict__ w, const float* __restrict__ scale,
                                          void* __restrict__ out, long long per_cout, long long total) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const float s = scale ? scale[i / per_cout] : 1.f;
-    WStore<T>::fprop(out, i, total, rounded_mul(w[i], s));
+    F::st(out, i, total, rounded_mul(w[i], s));
   }
 }
-// -> dgrad copy [Cin][taps][Cout]; blockIdx.z = tap; 32x32 LDS tile transpose
-template <typename T>
+// -> dgrad copy [Cin][taps][Cout] in the DGRAD format D; blockIdx.z = tap; 32x32 LDS tile transpose
+template <typename D>
 __global__ void weight_prep_dgrad_kernel(const float* __restrict__ w, const float* __restrict__ scale,
                                          void* __restrict__ out, int cout, int taps, int cin) {
   __shared__ float tile[32][33];
@@ -231,14 +219,14 @@ __global__ void weight_prep_dgrad_kernel(const float* __restrict__ w, const floa
   for (int j = threadIdx.y; j < 32; j += blockDim.y) {
     int ci = ci0 + j, co = co0 + threadIdx.x;
     if (co < cout && ci < cin)
-      wstore_dgrad<T>(out, ci, tap, co, taps, cout, (long long)cout * taps * cin, tile[threadIdx.x][j]);
+      D::st(out, ci, tap, co, taps, cout, (long long)cout * taps * cin, tile[threadIdx.x][j]);
   }
 }
 
 // All convolutions of the model in ONE launch: blockIdx.x walks 32x32 (cout x cin) tiles of every
 // (layer, tap); the tile is read once (coalesced along cin) and written twice: fprop order
 // [cout][tap][cin] and dgrad order [cin][tap][cout] (transposed through LDS).
-template <typename T>
+template <typename F, typename D>
 __global__ void weight_prep_batched_kernel(const vlfb_wprep_item* __restrict__ items, int n_items) {
   __shared__ float tile[32][33];
   const int b = blockIdx.x;
@@ -264,7 +252,7 @@ __global__ void weight_prep_batched_kernel(const vlfb_wprep_item* __restrict__ i
       const long long idx = ((long long)co * it.taps + tap) * it.cin + ci;
       const float v = rounded_mul(w[idx], scale ? scale[co] : 1.f);     // (no fma contraction into the term remainders)
       tile[j][threadIdx.x] = v;
-      if (wf) WStore<T>::fprop(wf, idx, plane, v);
+      if (wf) F::st(wf, idx, plane, v);
     }
   }
   if (!wd) return;
@@ -272,8 +260,40 @@ __global__ void weight_prep_batched_kernel(const vlfb_wprep_item* __restrict__ i
   for (int j = threadIdx.y; j < 32; j += blockDim.y) {
     const int ci = ci0 + j, co = co0 + threadIdx.x;
     if (co < it.cout && ci < it.cin)
-      wstore_dgrad<T>(wd, ci, tap, co, it.taps, it.cout, plane, tile[threadIdx.x][j]);
+      D::st(wd, ci, tap, co, it.taps, it.cout, plane, tile[threadIdx.x][j]);
   }
+}
+
+// THE table of weight codes, in the order of include/vlfb.h: code -> (FPROP copy format, DGRAD copy format).  Runs
+// f(F{}, D{}); false, and no call, for a code that names no weight format.
+template <typename Fn>
+bool with_weight_format(int code, Fn&& f) {
+  switch (code) {
+    case VLFB_F32: f(WfElems<float>{}, WdElems<float>{}); return true;
+    case VLFB_BF16: f(WfElems<bf16_t>{}, WdElems<bf16_t>{}); return true;
+    case VLFB_F16: f(WfElems<f16_t>{}, WdElems<f16_t>{}); return true;
+    case VLFB_SPLIT: f(WfTerms3{}, WdTerms2{}); return true;
+    case VLFB_MIX: f(WfTerms3{}, WdElems<f16_t>{}); return true;
+    case VLFB_MIX_W2: f(WfTerms3{}, WdScaled2{}); return true;
+    case VLFB_MIXH: f(WfScaled2{}, WdElems<f16_t>{}); return true;
+    case VLFB_MIXH_W2: f(WfScaled2{}, WdScaled2{}); return true;
+    case VLFB_MIX_W2I: f(WfTerms3{}, WdScaled2I{}); return true;
+    case VLFB_MIXH_W2I: f(WfScaled2{}, WdScaled2I{}); return true;
+    default: return false;
+  }
+}
+template <typename F, typename D>
+int weight_prep_as(const float* w, const float* scale, void* w_fprop, void* w_dgrad, int64_t cout, int64_t taps, int64_t cin, hipStream_t s) {
+  VLFB_REQUIRE(!w_dgrad || cout % D::kCoutMultiple == 0, "weight_prep: the interleaved two-term DGRAD copy needs Cout %% 64 == 0");
+  VLFB_REQUIRE(taps < 65536, "weight_prep: too many taps");
+  const long long total = cout * taps * cin;
+  if (w_fprop)
+    hipLaunchKernelGGL(weight_prep_fprop_kernel<F>, dim3(grid_for(total, 256)), dim3(256), 0, s, w, scale, w_fprop, (long long)(taps * cin), total);
+  if (w_dgrad) {
+    dim3 grid((unsigned)((cin + 31) / 32), (unsigned)((cout + 31) / 32), (unsigned)taps);
+    hipLaunchKernelGGL(weight_prep_dgrad_kernel<D>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin);
+  }
+  return check_launch("weight_prep");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1240,26 +1260,24 @@ extern "C" int vlfb_ncthw_to_nthwc(const float* src, void* dst, int dtype, int64
                                    int64_t thw, int64_t c_pad, vlfb_stream_t stream) {
   VLFB_REQUIRE(src && dst && c_pad >= c && n > 0 && c > 0 && thw > 0, "ncthw_to_nthwc: bad args");
   int grid = grid_for(n * thw, 256);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(ncthw_to_nthwc_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       src, (float*)dst, (long long)n, (int)c, (long long)thw, (int)c_pad);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(ncthw_to_nthwc_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       src, (T16*)dst, (long long)n, (int)c, (long long)thw, (int)c_pad));
-  else return set_error(VLFB_ERR_ARG, "ncthw_to_nthwc: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(ncthw_to_nthwc_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, (long long)n, (int)c,
+                           (long long)thw, (int)c_pad);
+      }))
+    return set_error(VLFB_ERR_ARG, "ncthw_to_nthwc: bad dtype");
   return check_launch("ncthw_to_nthwc");
 }
 extern "C" int vlfb_nthwc_to_ncthw(const void* src, float* dst, int dtype, int64_t n, int64_t c,
                                    int64_t thw, vlfb_stream_t stream) {
   VLFB_REQUIRE(src && dst && n > 0 && c > 0 && thw > 0, "nthwc_to_ncthw: bad args");
   int grid = grid_for(n * c * thw, 256);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(nthwc_to_ncthw_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)src, dst, (long long)n, (int)c, (long long)thw);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(nthwc_to_ncthw_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
-                       (const T16*)src, dst, (long long)n, (int)c, (long long)thw));
-  else return set_error(VLFB_ERR_ARG, "nthwc_to_ncthw: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(nthwc_to_ncthw_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, dst, (long long)n, (int)c,
+                           (long long)thw);
+      }))
+    return set_error(VLFB_ERR_ARG, "nthwc_to_ncthw: bad dtype");
   return check_launch("nthwc_to_ncthw");
 }
 // fp32 -> fp16 copy for the "mix" engine's backward (16 bytes read, 8 written per lane and step; positive values stay
@@ -1312,50 +1330,23 @@ extern "C" int vlfb_transpose2d(const void* src, void* dst, int dtype, int64_t b
   VLFB_REQUIRE(batch < 65536 && (rows + 31) / 32 < 65536, "transpose2d: grid too large");
   dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32), (unsigned)batch);
   dim3 block(32, 8);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(transpose2d_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)src, (float*)dst, (long long)rows, (long long)cols);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(transpose2d_kernel<T16>, grid, block, 0, (hipStream_t)stream, (const T16*)src, (T16*)dst, (long long)rows, (long long)cols));
-  else return set_error(VLFB_ERR_ARG, "transpose2d: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(transpose2d_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)src, (T*)dst, (long long)rows, (long long)cols);
+      }))
+    return set_error(VLFB_ERR_ARG, "transpose2d: bad dtype");
   return check_launch("transpose2d");
 }
 extern "C" int vlfb_weight_prep(const float* w, const float* scale, void* w_fprop, void* w_dgrad,
                                 int dtype, int64_t cout, int64_t taps, int64_t cin,
                                 vlfb_stream_t stream) {
   VLFB_REQUIRE(w && (w_fprop || w_dgrad) && cout > 0 && taps > 0 && cin > 0, "weight_prep: bad args");
-  VLFB_REQUIRE(dtype == VLFB_F32 || is16(dtype) || dtype == VLFB_SPLIT || dtype == VLFB_MIX || dtype == VLFB_MIX_W2 || dtype == VLFB_MIXH ||
-                   dtype == VLFB_MIXH_W2 || dtype == VLFB_MIX_W2I || dtype == VLFB_MIXH_W2I, "weight_prep: bad dtype");
-  VLFB_REQUIRE((dtype != VLFB_MIX_W2I && dtype != VLFB_MIXH_W2I) || !w_dgrad || cout % 64 == 0, "weight_prep: the interleaved two-term DGRAD copy needs Cout %% 64 == 0");
-  VLFB_REQUIRE(taps < 65536, "weight_prep: too many taps");
-  hipStream_t s = (hipStream_t)stream;
-  const long long total = cout * taps * cin;
-  if (w_fprop) {
-    int grid = grid_for(total, 256);
-    if (dtype == VLFB_F32)
-      hipLaunchKernelGGL(weight_prep_fprop_kernel<float>, dim3(grid), dim3(256), 0, s, w, scale, w_fprop, (long long)(taps * cin), total);
-    else if (dtype == VLFB_SPLIT || dtype == VLFB_MIX || dtype == VLFB_MIX_W2 || dtype == VLFB_MIX_W2I)
-      hipLaunchKernelGGL(weight_prep_fprop_kernel<SplitW>, dim3(grid), dim3(256), 0, s, w, scale, w_fprop, (long long)(taps * cin), total);
-    else if (dtype == VLFB_MIXH || dtype == VLFB_MIXH_W2 || dtype == VLFB_MIXH_W2I)
-      hipLaunchKernelGGL(weight_prep_fprop_kernel<MixHW>, dim3(grid), dim3(256), 0, s, w, scale, w_fprop, (long long)(taps * cin), total);
-    else
-      VLFB_WITH_T16(dtype, hipLaunchKernelGGL(weight_prep_fprop_kernel<T16>, dim3(grid), dim3(256), 0, s, w, scale, w_fprop, (long long)(taps * cin), total));
-  }
-  if (w_dgrad) {
-    dim3 grid((unsigned)((cin + 31) / 32), (unsigned)((cout + 31) / 32), (unsigned)taps);
-    if (dtype == VLFB_F32)
-      hipLaunchKernelGGL(weight_prep_dgrad_kernel<float>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin);
-    else if (dtype == VLFB_SPLIT)
-      hipLaunchKernelGGL(weight_prep_dgrad_kernel<SplitW>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin);
-    else if (dtype == VLFB_MIX || dtype == VLFB_MIXH)
-      hipLaunchKernelGGL(weight_prep_dgrad_kernel<MixW>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin);
-    else if (dtype == VLFB_MIX_W2 || dtype == VLFB_MIXH_W2)
-      hipLaunchKernelGGL(weight_prep_dgrad_kernel<MixW2>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin);
-    else if (dtype == VLFB_MIX_W2I || dtype == VLFB_MIXH_W2I)
-      hipLaunchKernelGGL(weight_prep_dgrad_kernel<MixW2I>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin);
-    else
-      VLFB_WITH_T16(dtype, hipLaunchKernelGGL(weight_prep_dgrad_kernel<T16>, grid, dim3(32, 8), 0, s, w, scale, w_dgrad, (int)cout, (int)taps, (int)cin));
-  }
-  return check_launch("weight_prep");
+  int rc = VLFB_OK;
+  if (!with_weight_format(dtype, [&](auto f, auto d) {
+        rc = weight_prep_as<decltype(f), decltype(d)>(w, scale, w_fprop, w_dgrad, cout, taps, cin, (hipStream_t)stream);
+      }))
+    return set_error(VLFB_ERR_ARG, "weight_prep: bad dtype");
+  return rc;
 }
 
 extern "C" int vlfb_pool_argmax_bytes(const vlfb_pool_desc* d) {
@@ -1372,71 +1363,55 @@ extern "C" int vlfb_maxpool_fwd(const vlfb_pool_desc* d, const void* x, void* y,
   int grid = grid_for((long long)p.N * p.To * p.Ho * p.Wo * (p.C / v), 256);
   hipStream_t s = (hipStream_t)stream;
   if (d->dtype == VLFB_F16PAIR) {
-    if (!wide) hipLaunchKernelGGL((maxpool_fwd_pair_kernel<uint8_t>), dim3(grid), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, (uint8_t*)argmax, p);
-    else hipLaunchKernelGGL((maxpool_fwd_pair_kernel<uint16_t>), dim3(grid), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, (uint16_t*)argmax, p);
+    with_argmax(wide, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((maxpool_fwd_pair_kernel<I>), dim3(grid), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, (I*)argmax, p);
+    });
     return check_launch("maxpool_fwd (fp16 planes)");
   }
-  if (d->dtype == VLFB_F32 && !wide)
-    hipLaunchKernelGGL((maxpool_fwd_kernel<float, uint8_t>), dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, (uint8_t*)argmax, p);
-  else if (d->dtype == VLFB_F32)
-    hipLaunchKernelGGL((maxpool_fwd_kernel<float, uint16_t>), dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, (uint16_t*)argmax, p);
-  else if (!wide)
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((maxpool_fwd_kernel<T16, uint8_t>), dim3(grid), dim3(256), 0, s, (const T16*)x, (T16*)y, (uint8_t*)argmax, p));
-  else
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((maxpool_fwd_kernel<T16, uint16_t>), dim3(grid), dim3(256), 0, s, (const T16*)x, (T16*)y, (uint16_t*)argmax, p));
+  with_elem(d->dtype, [&](auto t) {
+    with_argmax(wide, [&](auto i) {
+      using T = decltype(t);
+      using I = decltype(i);
+      hipLaunchKernelGGL((maxpool_fwd_kernel<T, I>), dim3(grid), dim3(256), 0, s, (const T*)x, (T*)y, (I*)argmax, p);
+    });
+  });
   return check_launch("maxpool_fwd");
+}
+// max-pool backward: the gradient gathered through the arg-max, plus `add` and masked by `mask > 0` (vlfb_maxpool_bwd), or
+// masked by the pooled values `y` themselves (vlfb_maxpool_relu_bwd); the pointers the other form has are null
+static int maxpool_bwd_impl(const vlfb_pool_desc* d, const void* dy, const void* argmax, void* dx, const void* add, const void* mask,
+                            const void* y, hipStream_t s, const char* what_fixed, const char* what) {
+  PoolP p = to_poolp(d);
+  const int v = d->dtype == VLFB_F32 ? 4 : 8;
+  const bool wide = vlfb_pool_argmax_bytes(d) == 2;
+  int grid = grid_for((long long)p.N * p.Ti * p.Hi * p.Wi * (p.C / v), 256);
+  bool fixed = false;
+  if (!with_elem(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        if (!wide && (fixed = launch_maxpool_bwd_fixed<T>(p, dy, argmax, dx, add, mask, y, s))) return;
+        with_argmax(wide, [&](auto i) {
+          using I = decltype(i);
+          hipLaunchKernelGGL((pool_bwd_kernel<T, true, I>), dim3(grid), dim3(256), 0, s, (const T*)dy, (const I*)argmax, (T*)dx, (const T*)add,
+                             (const T*)mask, p, 1.f, (const T*)y);
+        });
+      }))
+    return set_error(VLFB_ERR_ARG, "pool: bad dtype");        // (VLFB_F16PAIR: the backward runs on one plane)
+  return check_launch(fixed ? what_fixed : what);
 }
 extern "C" int vlfb_maxpool_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax,
                                 void* dx, const void* add, const void* mask, vlfb_stream_t stream) {
   int rc = check_pool(d);
   if (rc) return rc;
   VLFB_REQUIRE(dy && argmax && dx, "maxpool_bwd: null pointer");
-  PoolP p = to_poolp(d);
-  const int v = d->dtype == VLFB_F32 ? 4 : 8;
-  const bool wide = vlfb_pool_argmax_bytes(d) == 2;
-  int grid = grid_for((long long)p.N * p.Ti * p.Hi * p.Wi * (p.C / v), 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (!wide) {
-    bool done;
-    if (d->dtype == VLFB_F32) done = launch_maxpool_bwd_fixed<float>(p, dy, argmax, dx, add, mask, nullptr, s);
-    else VLFB_WITH_T16(d->dtype, done = launch_maxpool_bwd_fixed<T16>(p, dy, argmax, dx, add, mask, nullptr, s));
-    if (done) return check_launch("maxpool_bwd (fixed window)");
-  }
-  if (d->dtype == VLFB_F32 && !wide)
-    hipLaunchKernelGGL((pool_bwd_kernel<float, true, uint8_t>), dim3(grid), dim3(256), 0, s, (const float*)dy, (const uint8_t*)argmax, (float*)dx, (const float*)add, (const float*)mask, p, 1.f);
-  else if (d->dtype == VLFB_F32)
-    hipLaunchKernelGGL((pool_bwd_kernel<float, true, uint16_t>), dim3(grid), dim3(256), 0, s, (const float*)dy, (const uint16_t*)argmax, (float*)dx, (const float*)add, (const float*)mask, p, 1.f);
-  else if (!wide)
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((pool_bwd_kernel<T16, true, uint8_t>), dim3(grid), dim3(256), 0, s, (const T16*)dy, (const uint8_t*)argmax, (T16*)dx, (const T16*)add, (const T16*)mask, p, 1.f));
-  else
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((pool_bwd_kernel<T16, true, uint16_t>), dim3(grid), dim3(256), 0, s, (const T16*)dy, (const uint16_t*)argmax, (T16*)dx, (const T16*)add, (const T16*)mask, p, 1.f));
-  return check_launch("maxpool_bwd");
+  return maxpool_bwd_impl(d, dy, argmax, dx, add, mask, nullptr, (hipStream_t)stream, "maxpool_bwd (fixed window)", "maxpool_bwd");
 }
 extern "C" int vlfb_maxpool_relu_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax, const void* y,
                                      void* dx, vlfb_stream_t stream) {
   int rc = check_pool(d);
   if (rc) return rc;
   VLFB_REQUIRE(dy && argmax && dx && y, "maxpool_relu_bwd: null pointer");
-  PoolP p = to_poolp(d);
-  const int v = d->dtype == VLFB_F32 ? 4 : 8;
-  const bool wide = vlfb_pool_argmax_bytes(d) == 2;
-  int grid = grid_for((long long)p.N * p.Ti * p.Hi * p.Wi * (p.C / v), 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (!wide) {
-    bool done;
-    if (d->dtype == VLFB_F32) done = launch_maxpool_bwd_fixed<float>(p, dy, argmax, dx, nullptr, nullptr, y, s);
-    else VLFB_WITH_T16(d->dtype, done = launch_maxpool_bwd_fixed<T16>(p, dy, argmax, dx, nullptr, nullptr, y, s));
-    if (done) return check_launch("maxpool_relu_bwd (fixed window)");
-  }
-  if (d->dtype == VLFB_F32 && !wide)
-    hipLaunchKernelGGL((pool_bwd_kernel<float, true, uint8_t>), dim3(grid), dim3(256), 0, s, (const float*)dy, (const uint8_t*)argmax, (float*)dx, (const float*)nullptr, (const float*)nullptr, p, 1.f, (const float*)y);
-  else if (d->dtype == VLFB_F32)
-    hipLaunchKernelGGL((pool_bwd_kernel<float, true, uint16_t>), dim3(grid), dim3(256), 0, s, (const float*)dy, (const uint16_t*)argmax, (float*)dx, (const float*)nullptr, (const float*)nullptr, p, 1.f, (const float*)y);
-  else if (!wide)
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((pool_bwd_kernel<T16, true, uint8_t>), dim3(grid), dim3(256), 0, s, (const T16*)dy, (const uint8_t*)argmax, (T16*)dx, (const T16*)nullptr, (const T16*)nullptr, p, 1.f, (const T16*)y));
-  else
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((pool_bwd_kernel<T16, true, uint16_t>), dim3(grid), dim3(256), 0, s, (const T16*)dy, (const uint16_t*)argmax, (T16*)dx, (const T16*)nullptr, (const T16*)nullptr, p, 1.f, (const T16*)y));
-  return check_launch("maxpool_relu_bwd");
+  return maxpool_bwd_impl(d, dy, argmax, dx, nullptr, nullptr, y, (hipStream_t)stream, "maxpool_relu_bwd (fixed window)", "maxpool_relu_bwd");
 }
 extern "C" int vlfb_avgpool_fwd(const vlfb_pool_desc* d, const void* x, void* y, vlfb_stream_t stream) {
   int rc = check_pool(d);
@@ -1457,20 +1432,16 @@ extern "C" int vlfb_avgpool_fwd(const vlfb_pool_desc* d, const void* x, void* y,
       hipLaunchKernelGGL(avgpool_fwd_pair_kernel, dim3(grid_for((long long)p.N * p.To * p.Ho * p.Wo * (p.C / 8), 256)), dim3(256), 0, s, (const f16_t*)x, (float*)y, p);
     return check_launch("avgpool_fwd (fp16 planes)");
   }
-  if (global && p.N < 65536) {
-    dim3 grid((unsigned)((p.C / v + 7) / 8), (unsigned)p.N);
-    const long long rows = (long long)p.Ti * p.Hi * p.Wi;
-    if (d->dtype == VLFB_F32)
-      hipLaunchKernelGGL(global_avgpool_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (float*)y, rows, p.C);
-    else
-      VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL(global_avgpool_kernel<T16>, grid, dim3(256), 0, s, (const T16*)x, (T16*)y, rows, p.C));
-  } else {
-    int grid = grid_for((long long)p.N * p.To * p.Ho * p.Wo * (p.C / v), 256);
-    if (d->dtype == VLFB_F32)
-      hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)x, (float*)y, p);
-    else
-      VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL(avgpool_fwd_kernel<T16>, dim3(grid), dim3(256), 0, s, (const T16*)x, (T16*)y, p));
-  }
+  with_elem(d->dtype, [&](auto t) {       // (check_pool: one of the three element types from here on)
+    using T = decltype(t);
+    if (global && p.N < 65536) {
+      dim3 grid((unsigned)((p.C / v + 7) / 8), (unsigned)p.N);
+      hipLaunchKernelGGL(global_avgpool_kernel<T>, grid, dim3(256), 0, s, (const T*)x, (T*)y, (long long)p.Ti * p.Hi * p.Wi, p.C);
+    } else {
+      int grid = grid_for((long long)p.N * p.To * p.Ho * p.Wo * (p.C / v), 256);
+      hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)x, (T*)y, p);
+    }
+  });
   return check_launch("avgpool_fwd");
 }
 extern "C" int vlfb_avgpool_bwd(const vlfb_pool_desc* d, const void* dy, void* dx, const void* add,
@@ -1483,10 +1454,12 @@ extern "C" int vlfb_avgpool_bwd(const vlfb_pool_desc* d, const void* dy, void* d
   const int v = d->dtype == VLFB_F32 ? 4 : 8;
   const float inv = 1.0f / (float)(p.kt * p.kh * p.kw);
   int grid = grid_for((long long)p.N * p.Ti * p.Hi * p.Wi * (p.C / v), 256);
-  if (d->dtype == VLFB_F32)
-    hipLaunchKernelGGL((pool_bwd_kernel<float, false, uint8_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const uint8_t*)nullptr, (float*)dx, (const float*)add, (const float*)mask, p, inv);
-  else
-    VLFB_WITH_T16(d->dtype, hipLaunchKernelGGL((pool_bwd_kernel<T16, false, uint8_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T16*)dy, (const uint8_t*)nullptr, (T16*)dx, (const T16*)add, (const T16*)mask, p, inv));
+  if (!with_elem(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pool_bwd_kernel<T, false, uint8_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
+                           (const uint8_t*)nullptr, (T*)dx, (const T*)add, (const T*)mask, p, inv);
+      }))
+    return set_error(VLFB_ERR_ARG, "pool: bad dtype");        // (VLFB_F16PAIR: the backward runs on one plane)
   return check_launch("avgpool_bwd");
 }
 
@@ -1561,24 +1534,17 @@ extern "C" int vlfb_avgpool_bwd_two_term(const vlfb_pool_desc* d, const float* d
 extern "C" int vlfb_softmax_fwd(const float* s, void* p, int dtype, int64_t rows, int64_t cols,
                                 float scale, vlfb_stream_t stream) {
   VLFB_REQUIRE(s && p && rows > 0 && cols > 0 && cols < (1ll << 31), "softmax_fwd: bad args");
-  int grid = grid_for(rows * 64, 256);
-  if (cols % 4 == 0 && cols <= 64 * 4 * 8 && (dtype == VLFB_F32 || is16(dtype))) {
-    hipStream_t st = (hipStream_t)stream;
-    const bool small = cols <= 64 * 4 * 4;
-    if (dtype == VLFB_F32) {
-      if (small) hipLaunchKernelGGL((softmax_fwd_rowreg_kernel<float, 4>), dim3(grid), dim3(256), 0, st, s, (float*)p, (long long)rows, (int)cols, scale);
-      else hipLaunchKernelGGL((softmax_fwd_rowreg_kernel<float, 8>), dim3(grid), dim3(256), 0, st, s, (float*)p, (long long)rows, (int)cols, scale);
-    } else {
-      if (small) VLFB_WITH_T16(dtype, hipLaunchKernelGGL((softmax_fwd_rowreg_kernel<T16, 4>), dim3(grid), dim3(256), 0, st, s, (T16*)p, (long long)rows, (int)cols, scale));
-      else VLFB_WITH_T16(dtype, hipLaunchKernelGGL((softmax_fwd_rowreg_kernel<T16, 8>), dim3(grid), dim3(256), 0, st, s, (T16*)p, (long long)rows, (int)cols, scale));
-    }
-    return check_launch("softmax_fwd");
-  }
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(softmax_fwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, s, (float*)p, (long long)rows, (int)cols, scale);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(softmax_fwd_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, s, (T16*)p, (long long)rows, (int)cols, scale));
-  else return set_error(VLFB_ERR_ARG, "softmax_fwd: bad dtype");
+  const dim3 grid(grid_for(rows * 64, 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  // rows of at most 1024 / 2048 columns stay in registers (4 / 8 values per lane); longer or ragged rows are re-read
+  const bool rowreg = cols % 4 == 0 && cols <= 64 * 4 * 8, small = cols <= 64 * 4 * 4;
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (rowreg && small) hipLaunchKernelGGL((softmax_fwd_rowreg_kernel<T, 4>), grid, block, 0, st, s, (T*)p, (long long)rows, (int)cols, scale);
+        else if (rowreg) hipLaunchKernelGGL((softmax_fwd_rowreg_kernel<T, 8>), grid, block, 0, st, s, (T*)p, (long long)rows, (int)cols, scale);
+        else hipLaunchKernelGGL(softmax_fwd_kernel<T>, grid, block, 0, st, s, (T*)p, (long long)rows, (int)cols, scale);
+      }))
+    return set_error(VLFB_ERR_ARG, "softmax_fwd: bad dtype");
   return check_launch("softmax_fwd");
 }
 // probabilities in fp32, ds in a 16-bit type (the "mix" path: the softmax Jacobian cancels the common part of dP, so P
@@ -1598,24 +1564,16 @@ extern "C" int vlfb_softmax_bwd_p32(const float* dp, const float* p, void* ds, i
 extern "C" int vlfb_softmax_bwd(const float* dp, const void* p, void* ds, int dtype, int64_t rows,
                                 int64_t cols, float scale, vlfb_stream_t stream) {
   VLFB_REQUIRE(dp && p && ds && rows > 0 && cols > 0 && cols < (1ll << 31), "softmax_bwd: bad args");
-  int grid = grid_for(rows * 64, 256);
-  if (cols % 4 == 0 && cols <= 64 * 4 * 8 && (dtype == VLFB_F32 || is16(dtype))) {
-    hipStream_t st = (hipStream_t)stream;
-    const bool small = cols <= 64 * 4 * 4;
-    if (dtype == VLFB_F32) {
-      if (small) hipLaunchKernelGGL((softmax_bwd_rowreg_kernel<float, 4>), dim3(grid), dim3(256), 0, st, dp, (const float*)p, (float*)ds, (long long)rows, (int)cols, scale);
-      else hipLaunchKernelGGL((softmax_bwd_rowreg_kernel<float, 8>), dim3(grid), dim3(256), 0, st, dp, (const float*)p, (float*)ds, (long long)rows, (int)cols, scale);
-    } else {
-      if (small) VLFB_WITH_T16(dtype, hipLaunchKernelGGL((softmax_bwd_rowreg_kernel<T16, 4>), dim3(grid), dim3(256), 0, st, dp, (const T16*)p, (T16*)ds, (long long)rows, (int)cols, scale));
-      else VLFB_WITH_T16(dtype, hipLaunchKernelGGL((softmax_bwd_rowreg_kernel<T16, 8>), dim3(grid), dim3(256), 0, st, dp, (const T16*)p, (T16*)ds, (long long)rows, (int)cols, scale));
-    }
-    return check_launch("softmax_bwd");
-  }
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(softmax_bwd_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dp, (const float*)p, (float*)ds, (long long)rows, (int)cols, scale);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(softmax_bwd_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, dp, (const T16*)p, (T16*)ds, (long long)rows, (int)cols, scale));
-  else return set_error(VLFB_ERR_ARG, "softmax_bwd: bad dtype");
+  const dim3 grid(grid_for(rows * 64, 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const bool rowreg = cols % 4 == 0 && cols <= 64 * 4 * 8, small = cols <= 64 * 4 * 4;       // (as vlfb_softmax_fwd)
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (rowreg && small) hipLaunchKernelGGL((softmax_bwd_rowreg_kernel<T, 4>), grid, block, 0, st, dp, (const T*)p, (T*)ds, (long long)rows, (int)cols, scale);
+        else if (rowreg) hipLaunchKernelGGL((softmax_bwd_rowreg_kernel<T, 8>), grid, block, 0, st, dp, (const T*)p, (T*)ds, (long long)rows, (int)cols, scale);
+        else hipLaunchKernelGGL(softmax_bwd_kernel<T>, grid, block, 0, st, dp, (const T*)p, (T*)ds, (long long)rows, (int)cols, scale);
+      }))
+    return set_error(VLFB_ERR_ARG, "softmax_bwd: bad dtype");
   return check_launch("softmax_bwd");
 }
 
@@ -1625,11 +1583,11 @@ extern "C" int vlfb_add(const void* a, const void* b, void* y, const void* mask,
   if (n == 0) return VLFB_OK;
   const int v = dtype == VLFB_F32 ? 4 : 8;
   int grid = grid_for((n + v - 1) / v, 256);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(add_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)y, (const float*)mask, (long long)n, relu);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(add_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T16*)a, (const T16*)b, (T16*)y, (const T16*)mask, (long long)n, relu));
-  else return set_error(VLFB_ERR_ARG, "add: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(add_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (T*)y, (const T*)mask, (long long)n, relu);
+      }))
+    return set_error(VLFB_ERR_ARG, "add: bad dtype");
   return check_launch("add");
 }
 extern "C" int vlfb_relu_fwd(const void* x, void* y, int dtype, int64_t n, vlfb_stream_t stream) {
@@ -1655,10 +1613,10 @@ int colsum_partials(const void* g, int dtype, long long rows, long long cols, lo
   const int v = dtype == VLFB_F32 ? 4 : 8;
   VLFB_REQUIRE(g && partials && rows > 0 && cols > 0 && ld >= cols && cols % v == 0 && ld % v == 0 && dtype_ok(dtype), "colsum_partials: bad args");
   dim3 grid((unsigned)((cols / v + 7) / 8), (unsigned)colsum_slabs(dtype, rows, cols));
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL((colsum_kernel<float, true>), grid, dim3(256), 0, s, (const float*)g, rows, (int)cols, ld, partials);
-  else
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL((colsum_kernel<T16, true>), grid, dim3(256), 0, s, (const T16*)g, rows, (int)cols, ld, partials));
+  with_elem(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((colsum_kernel<T, true>), grid, dim3(256), 0, s, (const T*)g, rows, (int)cols, ld, partials);
+  });
   return check_launch("colsum (partials)");
 }
 }  // namespace vlfb
@@ -1679,11 +1637,10 @@ extern "C" int vlfb_colsum(const void* g, int dtype, int64_t rows, int64_t cols,
   if (slabs > want) slabs = want;
   if (slabs < 1) slabs = 1;
   dim3 grid((unsigned)cblocks, (unsigned)slabs);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)g, (long long)rows, (int)cols, (long long)ld, out);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(colsum_kernel<T16>, grid, dim3(256), 0, s, (const T16*)g, (long long)rows, (int)cols, (long long)ld, out));
-  else return set_error(VLFB_ERR_ARG, "colsum: bad dtype");
+  with_elem(dtype, [&](auto t) {          // (dtype_ok above)
+    using T = decltype(t);
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, s, (const T*)g, (long long)rows, (int)cols, (long long)ld, out);
+  });
   return check_launch("colsum");
 }
 
@@ -1691,11 +1648,11 @@ extern "C" int vlfb_copy2d(const void* src, int64_t lds, void* dst, int64_t ldd,
                            int64_t rows, int64_t cols, vlfb_stream_t stream) {
   VLFB_REQUIRE(src && dst && rows > 0 && cols > 0 && lds >= cols && ldd >= cols, "copy2d: bad args");
   int grid = grid_for(rows * cols, 256);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(copy2d_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)src, (long long)lds, (float*)dst, (long long)ldd, (long long)rows, (long long)cols);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(copy2d_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T16*)src, (long long)lds, (T16*)dst, (long long)ldd, (long long)rows, (long long)cols));
-  else return set_error(VLFB_ERR_ARG, "copy2d: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(copy2d_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, (long long)lds, (T*)dst, (long long)ldd, (long long)rows, (long long)cols);
+      }))
+    return set_error(VLFB_ERR_ARG, "copy2d: bad dtype");
   return check_launch("copy2d");
 }
 extern "C" int vlfb_zero_f32(float* p, int64_t n, vlfb_stream_t stream) {
@@ -1708,26 +1665,13 @@ extern "C" int vlfb_zero_f32(float* p, int64_t n, vlfb_stream_t stream) {
 extern "C" int vlfb_weight_prep_batched(const vlfb_wprep_item* items_dev, int n_items, int total_tiles,
                                         int dtype, vlfb_stream_t stream) {
   VLFB_REQUIRE(items_dev && n_items > 0 && total_tiles > 0, "weight_prep_batched: bad args");
-  dim3 block(32, 8);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<float>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(weight_prep_batched_kernel<T16>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items));
-  else if (dtype == VLFB_SPLIT)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<SplitW>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (dtype == VLFB_MIX)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<MixW>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (dtype == VLFB_MIX_W2)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<MixW2>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (dtype == VLFB_MIXH)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<MixHW>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (dtype == VLFB_MIXH_W2)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<MixHW2>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (dtype == VLFB_MIX_W2I)      // (the caller keeps Cout % 64 == 0 for these items: vlfb_weight_prep checks it per conv)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<MixW2I>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else if (dtype == VLFB_MIXH_W2I)
-    hipLaunchKernelGGL(weight_prep_batched_kernel<MixHW2I>, dim3((unsigned)total_tiles), block, 0, (hipStream_t)stream, items_dev, n_items);
-  else return set_error(VLFB_ERR_ARG, "weight_prep_batched: bad dtype");
+  // (the items live on the device: the caller keeps Cout % 64 == 0 for those of an interleaved code, which
+  // vlfb_weight_prep checks per conv)
+  if (!with_weight_format(dtype, [&](auto f, auto d) {
+        hipLaunchKernelGGL((weight_prep_batched_kernel<decltype(f), decltype(d)>), dim3((unsigned)total_tiles), dim3(32, 8), 0,
+                           (hipStream_t)stream, items_dev, n_items);
+      }))
+    return set_error(VLFB_ERR_ARG, "weight_prep_batched: bad dtype");
   return check_launch("weight_prep_batched");
 }
 
@@ -1737,10 +1681,10 @@ extern "C" int vlfb_ncthw_to_nthwc_wpad(const float* src, void* dst, int dtype, 
   VLFB_REQUIRE(src && dst && c_pad >= c && n > 0 && c > 0 && rows > 0 && w > 0 && wpad_left >= 0 &&
                w_total >= wpad_left + w, "ncthw_to_nthwc_wpad: bad args");
   int grid = grid_for(n * rows * w_total, 256);
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(ncthw_to_nthwc_wpad_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (float*)dst, (long long)n, (int)c, (long long)rows, (int)w, (int)c_pad, (int)wpad_left, (int)w_total);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(ncthw_to_nthwc_wpad_kernel<T16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (T16*)dst, (long long)n, (int)c, (long long)rows, (int)w, (int)c_pad, (int)wpad_left, (int)w_total));
-  else return set_error(VLFB_ERR_ARG, "ncthw_to_nthwc_wpad: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(ncthw_to_nthwc_wpad_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, (long long)n, (int)c, (long long)rows, (int)w, (int)c_pad, (int)wpad_left, (int)w_total);
+      }))
+    return set_error(VLFB_ERR_ARG, "ncthw_to_nthwc_wpad: bad dtype");
   return check_launch("ncthw_to_nthwc_wpad");
 }

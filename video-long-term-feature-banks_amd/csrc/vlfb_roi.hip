@@ -217,11 +217,11 @@ extern "C" int vlfb_roi_align_max_fwd(const void* feat, int dtype, const float* 
   const int threads = nch * gr;
   const size_t lds = (size_t)gr * c * 5;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(roi_align_max_fwd_kernel<float>, dim3((unsigned)r), dim3(threads), lds, s, (const float*)feat, rois, (float*)out, argbin, dbg, (int)h, (int)w, (int)c, pooled, spatial_scale);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(roi_align_max_fwd_kernel<T16>, dim3((unsigned)r), dim3(threads), lds, s, (const T16*)feat, rois, (T16*)out, argbin, dbg, (int)h, (int)w, (int)c, pooled, spatial_scale));
-  else return set_error(VLFB_ERR_ARG, "roi_align_fwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(roi_align_max_fwd_kernel<T>, dim3((unsigned)r), dim3(threads), lds, s, (const T*)feat, rois, (T*)out, argbin, dbg, (int)h, (int)w, (int)c, pooled, spatial_scale);
+      }))
+    return set_error(VLFB_ERR_ARG, "roi_align_fwd: bad dtype");
   return check_launch("roi_align_max_fwd");
 }
 
@@ -267,10 +267,10 @@ extern "C" int vlfb_roi_align_max_bwd(const void* dout, int dtype, const float* 
   VLFB_REQUIRE(dout && rois && argbin && dfeat && n > 0 && h > 0 && w > 0 && c > 0 && r > 0, "roi_align_bwd: bad args");
   int grid = grid_for(n * c, 64);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VLFB_F32)
-    hipLaunchKernelGGL(roi_align_max_bwd_kernel<float>, dim3(grid), dim3(64), 0, s, (const float*)dout, rois, argbin, dfeat, (long long)n, (long long)r, (int)h, (int)w, (int)c, pooled, spatial_scale);
-  else if (is16(dtype))
-    VLFB_WITH_T16(dtype, hipLaunchKernelGGL(roi_align_max_bwd_kernel<T16>, dim3(grid), dim3(64), 0, s, (const T16*)dout, rois, argbin, dfeat, (long long)n, (long long)r, (int)h, (int)w, (int)c, pooled, spatial_scale));
-  else return set_error(VLFB_ERR_ARG, "roi_align_bwd: bad dtype");
+  if (!with_elem(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(roi_align_max_bwd_kernel<T>, dim3(grid), dim3(64), 0, s, (const T*)dout, rois, argbin, dfeat, (long long)n, (long long)r, (int)h, (int)w, (int)c, pooled, spatial_scale);
+      }))
+    return set_error(VLFB_ERR_ARG, "roi_align_bwd: bad dtype");
   return check_launch("roi_align_max_bwd");
 }

@@ -370,26 +370,14 @@ __global__ __launch_bounds__(512) void stem_fprop_pair_kernel(const GP p, const 
 }
 
 int launch_stem_fprop_pair_t(const GP& gp, int hblocks, int ntiles, int tpw, unsigned nwg, size_t lds, hipStream_t s) {
-  auto kernel = stem_fprop_pair_kernel<7, 7>;
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(512), lds, s, gp, hblocks, ntiles, tpw);
-  return check_launch("conv kernel (stem, direct, fp16 planes)");
+  return launch_lds<stem_fprop_pair_kernel<7, 7>, 160 * 1024>(dim3(nwg), dim3(512), lds, s, "conv kernel (stem, direct, fp16 planes)",
+                                                              gp, hblocks, ntiles, tpw);
 }
 
 template <typename T>
 int launch_stem_fprop_t(const GP& gp, int hblocks, int ntiles, int tpw, unsigned nwg, size_t lds, hipStream_t s) {
-  auto kernel = stem_fprop_kernel<T, 7, 7>;
-  static bool configured = false;   // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(512), lds, s, gp, hblocks, ntiles, tpw);
-  return check_launch("conv kernel (stem, direct)");
+  return launch_lds<stem_fprop_kernel<T, 7, 7>, 160 * 1024>(dim3(nwg), dim3(512), lds, s, "conv kernel (stem, direct)",
+                                                            gp, hblocks, ntiles, tpw);
 }
 
 }  // namespace
@@ -427,13 +415,7 @@ bool stem_fprop_pair_ok(const GP& gp, int pack_w, long long batch) {
 }
 
 int launch_stem_fprop_pair(const GP& gp, hipStream_t s) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    ncu = n / 8 * 8;
-  }
+  const int ncu = device_cus8();
   const int hblocks = (gp.Hr + kStemWaves - 1) / kStemWaves;
   const long long ntiles = (long long)(gp.M / (gp.Hr * gp.Wr)) * hblocks;
   long long nwg = (ntiles + 7) / 8 * 8;
@@ -445,13 +427,7 @@ int launch_stem_fprop_pair(const GP& gp, hipStream_t s) {
 }
 
 int launch_stem_fprop(const GP& gp, int dtype, hipStream_t s) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    ncu = n / 8 * 8;
-  }
+  const int ncu = device_cus8();
   const int hblocks = (gp.Hr + kStemWaves - 1) / kStemWaves;
   const long long ntiles = (long long)(gp.M / (gp.Hr * gp.Wr)) * hblocks;      // (n, t) frames x row blocks
   long long nwg = (ntiles + 7) / 8 * 8;

@@ -333,23 +333,18 @@ __global__ __launch_bounds__(512) void wgrad_rows_fat_kernel(const GP p) {
       }
 }
 
-template <typename K>
-void launch_rows(K kernel, const GP& gp, unsigned splits, unsigned threads, size_t lds, hipStream_t s) {
-  static bool configured = false;   // per template instance
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    configured = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(splits), dim3(threads), lds, s, gp);
+template <auto Kernel>
+int launch_rows(const GP& gp, unsigned splits, size_t lds, hipStream_t s, const char* what) {
+  return launch_lds<Kernel, 160 * 1024>(dim3(splits), dim3(512), lds, s, what, gp);
 }
 
 template <typename T>
-void launch_rows_t(const GP& gp, int ct, unsigned splits, hipStream_t s) {
+int launch_rows_t(const GP& gp, int ct, unsigned splits, hipStream_t s) {
   // 8 waves, one workgroup per CU: ring of 2 groups x 2 output rows x (3 + 1) staged rows x 8 KiB = 128 KiB
   constexpr size_t kLds = 2 * 2 * 4 * 64 * 128;
-  if (ct == 2) launch_rows(wgrad_rows_kernel<T, 2, 3, 2, 8, 2>, gp, splits, 512, kLds, s);
-  else launch_rows(wgrad_rows_kernel<T, 5, 3, 2, 8, 2>, gp, splits, 512, kLds, s);
+  const char* what = "conv wgrad (whole rows) kernel";
+  if (ct == 2) return launch_rows<wgrad_rows_kernel<T, 2, 3, 2, 8, 2>>(gp, splits, kLds, s, what);
+  return launch_rows<wgrad_rows_kernel<T, 5, 3, 2, 8, 2>>(gp, splits, kLds, s, what);
 }
 
 }  // namespace
@@ -363,17 +358,16 @@ int wgrad_rows_ct(long long K) {
 
 int launch_wgrad_rows_fat(const GP& gp, int splits, int dtype, hipStream_t s) {
   constexpr size_t kLds = 2 * (4 + 3) * 64 * 128;       // 2 rows x (4 X groups + 3 gradient rows) x 8 KiB
-  if (dtype == VLFB_F16) launch_rows(wgrad_rows_fat_kernel<f16_t, 4, 3>, gp, (unsigned)splits, 512, kLds, s);
-  else launch_rows(wgrad_rows_fat_kernel<bf16_t, 4, 3>, gp, (unsigned)splits, 512, kLds, s);
-  return check_launch("conv wgrad (whole rows, fat input) kernel");
+  const char* what = "conv wgrad (whole rows, fat input) kernel";
+  if (dtype == VLFB_F16) return launch_rows<wgrad_rows_fat_kernel<f16_t, 4, 3>>(gp, (unsigned)splits, kLds, s, what);
+  return launch_rows<wgrad_rows_fat_kernel<bf16_t, 4, 3>>(gp, (unsigned)splits, kLds, s, what);
 }
 
 int launch_wgrad_rows(const GP& gp, int splits, size_t lds, int dtype, hipStream_t s) {
   (void)lds;
   const int ct = wgrad_rows_ct(gp.K);
-  if (dtype == VLFB_F16) launch_rows_t<f16_t>(gp, ct, (unsigned)splits, s);
-  else launch_rows_t<bf16_t>(gp, ct, (unsigned)splits, s);
-  return check_launch("conv wgrad (whole rows) kernel");
+  if (dtype == VLFB_F16) return launch_rows_t<f16_t>(gp, ct, (unsigned)splits, s);
+  return launch_rows_t<bf16_t>(gp, ct, (unsigned)splits, s);
 }
 
 }  // namespace vlfb

@@ -323,24 +323,20 @@ class ConvStep(Step):
         FPROP, 2 for DGRAD -- include/vlfb.h VLFB_SPLIT; "mix": two-term or plain fp16 DGRAD copy, per conv --
         ConvStep._w2_geometry; a conv without a DGRAD copy goes with the engine's default)"""
         eng = self.eng
-        bf, hf = torch.bfloat16, torch.float16
         if not eng.mix:
-            return (hip.SPLIT, 3, bf, 2, bf) if eng.split else (eng.wcode, 1, eng.tdtype, 1, eng.tdtype)
-        dgrad = "none" if not has_dgrad else "fp32-head" if self.bwd_split else \
-            "interleaved" if self.w2i else "two-term" if self.w2 else "plain"
-        return {
-            # FPROP as split-bf16 products of the fp32 input: three bf16 term planes
-            (False, "none"): (eng.wcode, 3, bf, 1, hf),
-            (False, "plain"): (hip.MIX, 3, bf, 1, hf),
-            (False, "two-term"): (hip.MIX_W2, 3, bf, 2, hf),
-            (False, "interleaved"): (hip.MIX_W2I, 3, bf, 2, hf),
-            (False, "fp32-head"): (hip.SPLIT, 3, bf, 2, bf),
-            # a two-plane input: FPROP reads hi, lo of (w * s) * 2^10 in fp16 (a conv of the fp32 head never has one)
-            (True, "none"): (hip.MIXH_W2 if eng.MIX_W2 else hip.MIXH, 2, hf, 1, hf),
-            (True, "plain"): (hip.MIXH, 2, hf, 1, hf),
-            (True, "two-term"): (hip.MIXH_W2, 2, hf, 2, hf),
-            (True, "interleaved"): (hip.MIXH_W2I, 2, hf, 2, hf),
-        }[(self.x_pair, dgrad)]
+            wcode = eng.wcode
+        elif not has_dgrad:
+            wcode = (hip.MIXH_W2 if eng.MIX_W2 else hip.MIXH) if self.x_pair else eng.wcode
+        elif self.bwd_split:
+            wcode = hip.SPLIT                      # a conv of the fp32 head (never has a two-plane input)
+        elif self.x_pair:                          # FPROP reads hi, lo of (w * s) * 2^10 in fp16
+            wcode = hip.MIXH_W2I if self.w2i else hip.MIXH_W2 if self.w2 else hip.MIXH
+        else:                                      # FPROP as split-bf16 products of the fp32 input
+            wcode = hip.MIX_W2I if self.w2i else hip.MIX_W2 if self.w2 else hip.MIX
+        wf_npl, wf_type, wd_npl, wd_type = hip.WEIGHT_FORMATS[wcode]
+        if eng.mix and not has_dgrad:
+            wd_npl = 1                             # (no DGRAD copy is kept: what the conv-step snapshot records for these)
+        return wcode, wf_npl, wf_type, wd_npl, wd_type
 
     def _formats(self):
         """every format decision of this conv, each taken once: the flags, the keyword groups the descriptors share and the

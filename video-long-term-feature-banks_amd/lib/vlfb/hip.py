@@ -29,6 +29,20 @@ LIB_PATH = os.path.join(_HERE, "libvlfb_hip.so")
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 
+# The weight-operand formats, as csrc/vlfb_ops.hip with_weight_format: weight code -> (planes and type of the FPROP copy, planes
+# and type of the DGRAD copy) that vlfb_weight_prep* write, each copy [planes][Cout * taps * Cin] elements.
+_bf, _hf = torch.bfloat16, torch.float16
+WEIGHT_FORMATS = {
+    F32: (1, torch.float32, 1, torch.float32), BF16: (1, _bf, 1, _bf), F16: (1, _hf, 1, _hf),     # elements of the type itself
+    SPLIT: (3, _bf, 2, _bf),                        # bf16 term planes
+    MIX: (3, _bf, 1, _hf),                          # FPROP as SPLIT; DGRAD fp16 elements
+    MIX_W2: (3, _bf, 2, _hf),                       # ... two fp16 terms of v * 2^10, [Cin][term][taps][Cout]
+    MIX_W2I: (3, _bf, 2, _hf),                      # ... the same terms interleaved, [Cin][taps][Cout / 64][term][64]
+    MIXH: (2, _hf, 1, _hf),                         # FPROP two fp16 planes of v * 2^10; DGRAD as MIX
+    MIXH_W2: (2, _hf, 2, _hf),                      # ... as MIX_W2
+    MIXH_W2I: (2, _hf, 2, _hf),                     # ... as MIX_W2I
+}
+
 
 def dtype_code(t):
     if t == torch.float32:
