@@ -586,6 +586,23 @@ int vlfb_lfb_sample_compact(const vlfb_lfb_desc* d, const void* bank, const int3
 int vlfb_lfb_sample_packed(const vlfb_lfb_desc* d, const void* bank, const int32_t* count,
                            const int32_t* query, int64_t rows, int window, int max_per_step, void* out,
                            int out_dtype, vlfb_stream_t stream);
+/* Packed export: the occupied rows of the bank in cell order (video-major, then step), inside a cell in slot order
+ * (= append order), so that writing, loading and merging a bank touch only what it holds.
+ * offsets int64 [cells + 1], cells = n_videos * n_steps: offsets[c] = sum over cells before c (video-major, then step)
+ * of min(count, capacity); offsets[cells] = the number of features in the bank.  Integer scan, fixed order, no atomics.
+ * Two levels: tiles of VLFB_LFB_PACK_TILE cells scanned in LDS, one workgroup scans the tile totals (kept in `offsets`
+ * itself, no workspace), an add-back.  That covers cells <= VLFB_LFB_PACK_MAX_CELLS = TILE * TILE; more is VLFB_ERR_ARG
+ * (the AVA train bank has 235 * 900 = 211500 cells). */
+#define VLFB_LFB_PACK_TILE 1024
+#define VLFB_LFB_PACK_MAX_CELLS (VLFB_LFB_PACK_TILE * VLFB_LFB_PACK_TILE)
+int vlfb_lfb_pack_offsets(const vlfb_lfb_desc* d, const int32_t* count, int64_t* offsets, vlfb_stream_t stream);
+/* rows [first_row, first_row + rows) of the packed order (cell order, then slot order = append order) -> out [rows][dim] of
+ * out_dtype and keys [rows][2] = {video, step}: exactly what vlfb_lfb_append takes, so a packed chunk appended to an
+ * empty bank of the same geometry reproduces these cells bit for bit.  Rows at or beyond offsets[cells] are not written.
+ * `offsets` is what vlfb_lfb_pack_offsets wrote for the same `count`, earlier on the same stream; 0 <= rows < 2^20 per
+ * call as for vlfb_lfb_append, first_row >= 0. */
+int vlfb_lfb_pack(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, const int64_t* offsets,
+                  int64_t first_row, int64_t rows, void* out, int out_dtype, int32_t* keys, vlfb_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Clip preprocessing on the device.  Replaces the per-frame cv2 / NumPy chain of

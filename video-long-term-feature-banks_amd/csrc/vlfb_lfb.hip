@@ -195,6 +195,113 @@ __global__ void lfb_sample_packed_kernel(BankP b, const char* __restrict__ bank,
   }
 }
 
+// ---- packed export -----------------------------------------------------------------------------------------------------
+// offsets[c] = features held by the cells before c.  `count` is n_videos * n_steps int32 (L2-resident at every real
+// geometry): latency-bound, three short launches.  The tile totals live in `offsets` itself: the local exclusive scan of a
+// tile is 0 at the tile's first cell, so that entry holds the total of the tile BEFORE it until the second level turns the
+// totals into tile bases in place; the last total lands in offsets[cells].
+constexpr int kPackThreads = 256;
+constexpr int kPackPer = VLFB_LFB_PACK_TILE / kPackThreads;      // consecutive cells per thread
+
+// exclusive prefix of `v` over the workgroup's threads (Hillis-Steele in LDS, fixed order); *total = the workgroup's sum
+__device__ int64_t pack_block_exclusive(int64_t v, int64_t* total) {
+  __shared__ int64_t s[2][kPackThreads];
+  int cur = 0;
+  s[0][threadIdx.x] = v;
+  __syncthreads();
+  for (int d = 1; d < kPackThreads; d <<= 1) {
+    int64_t x = s[cur][threadIdx.x];
+    if ((int)threadIdx.x >= d) x += s[cur][threadIdx.x - d];
+    s[cur ^ 1][threadIdx.x] = x;
+    cur ^= 1;
+    __syncthreads();
+  }
+  *total = s[cur][kPackThreads - 1];
+  return s[cur][threadIdx.x] - v;
+}
+
+// level 1: one workgroup per tile; offsets[c] = local exclusive prefix for the cells behind the tile's first,
+// offsets[end of the tile] = the tile's total
+__global__ void __launch_bounds__(kPackThreads)
+lfb_pack_tile_scan_kernel(const int32_t* __restrict__ count, int capacity, int64_t cells, int64_t* offsets) {
+  const int64_t start = (int64_t)blockIdx.x * VLFB_LFB_PACK_TILE;
+  const int64_t c0 = start + (int64_t)threadIdx.x * kPackPer;
+  int64_t v[kPackPer], sum = 0;
+  for (int i = 0; i < kPackPer; ++i) {
+    int n = c0 + i < cells ? count[c0 + i] : 0;
+    n = n < 0 ? 0 : (n > capacity ? capacity : n);
+    v[i] = n;
+    sum += n;
+  }
+  int64_t total;
+  int64_t run = pack_block_exclusive(sum, &total);
+  for (int i = 0; i < kPackPer; ++i) {
+    const int64_t c = c0 + i;
+    if (c > start && c < cells) offsets[c] = run;
+    run += v[i];
+  }
+  if (threadIdx.x == 0) {
+    const int64_t end = start + VLFB_LFB_PACK_TILE < cells ? start + VLFB_LFB_PACK_TILE : cells;
+    offsets[end] = total;
+    if (blockIdx.x == 0) offsets[0] = 0;
+  }
+}
+
+// level 2: one workgroup; the totals at offsets[min(k * TILE, cells)], k = 1 .. tiles, become their inclusive prefix =
+// the base of tile k (and, for k = tiles, the number of features in the bank)
+__global__ void __launch_bounds__(kPackThreads)
+lfb_pack_totals_scan_kernel(int64_t cells, int tiles, int64_t* offsets) {
+  int64_t v[kPackPer], sum = 0;
+  for (int i = 0; i < kPackPer; ++i) {
+    const int k = (int)threadIdx.x * kPackPer + i + 1;
+    const int64_t p = (int64_t)k * VLFB_LFB_PACK_TILE < cells ? (int64_t)k * VLFB_LFB_PACK_TILE : cells;
+    v[i] = k <= tiles ? offsets[p] : 0;
+    sum += v[i];
+  }
+  int64_t total;
+  int64_t run = pack_block_exclusive(sum, &total);
+  for (int i = 0; i < kPackPer; ++i) {
+    const int k = (int)threadIdx.x * kPackPer + i + 1;
+    const int64_t p = (int64_t)k * VLFB_LFB_PACK_TILE < cells ? (int64_t)k * VLFB_LFB_PACK_TILE : cells;
+    run += v[i];
+    if (k <= tiles) offsets[p] = run;
+  }
+}
+
+// level 3: tile t = blockIdx.x + 1 adds its base offsets[t * TILE] to the cells behind its first
+__global__ void __launch_bounds__(kPackThreads)
+lfb_pack_add_base_kernel(int64_t cells, int64_t* offsets) {
+  const int64_t start = ((int64_t)blockIdx.x + 1) * VLFB_LFB_PACK_TILE;
+  const int64_t base = offsets[start];
+  for (int i = 0; i < kPackPer; ++i) {
+    const int64_t c = start + (int64_t)threadIdx.x * kPackPer + i;
+    if (c > start && c < start + VLFB_LFB_PACK_TILE && c < cells) offsets[c] += base;
+  }
+}
+
+// one workgroup per packed row g = first_row + blockIdx.x: its cell is the c with offsets[c] <= g < offsets[c + 1] (a
+// binary search every thread makes alike, so the loads are uniform), its slot g - offsets[c]
+__global__ void lfb_pack_kernel(BankP b, const char* __restrict__ bank, const int32_t* __restrict__ count,
+                                const int64_t* __restrict__ offsets, int64_t first_row, void* out, int odt, int32_t* keys) {
+  const int64_t cells = (int64_t)b.n_videos * b.n_steps;
+  const int64_t g = first_row + blockIdx.x;
+  if (g >= offsets[cells]) return;
+  int64_t lo = 0, hi = cells;             // offsets[lo] <= g < offsets[hi]
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (offsets[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int64_t slot = g - offsets[lo];
+  int n = count[lo];
+  n = n > b.capacity ? b.capacity : n;
+  if (slot < 0 || slot >= n) return;      // `offsets` does not belong to `count`: write nothing rather than read outside the cell
+  row_copy(out, odt, (long long)blockIdx.x * b.dim, bank, b.dtype, ((long long)lo * b.capacity + slot) * (long long)b.dim, b.dim);
+  if (threadIdx.x == 0) {
+    keys[2 * blockIdx.x] = (int32_t)(lo / b.n_steps);
+    keys[2 * blockIdx.x + 1] = (int32_t)(lo % b.n_steps);
+  }
+}
+
 int check_desc(const vlfb_lfb_desc* d, BankP* b) {
   VLFB_REQUIRE(d != nullptr, "lfb: descriptor is NULL");
   VLFB_REQUIRE(d->n_videos > 0 && d->n_steps > 0 && d->capacity > 0 && d->dim > 0, "lfb: empty bank geometry");
@@ -284,4 +391,37 @@ extern "C" int vlfb_lfb_sample_compact(const vlfb_lfb_desc* d, const void* bank,
                                        const int32_t* query, int64_t rows, int window, void* out,
                                        int out_dtype, vlfb_stream_t stream) {
   return vlfb_lfb_sample_packed(d, bank, count, query, rows, window, 1, out, out_dtype, stream);
+}
+
+extern "C" int vlfb_lfb_pack_offsets(const vlfb_lfb_desc* d, const int32_t* count, int64_t* offsets, vlfb_stream_t stream) {
+  BankP b;
+  int rc = check_desc(d, &b);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(count && offsets, "lfb_pack_offsets: NULL buffer");
+  const int64_t cells = (int64_t)b.n_videos * b.n_steps;
+  VLFB_REQUIRE(cells <= VLFB_LFB_PACK_MAX_CELLS, "lfb_pack_offsets: more than 2^20 cells (the two scan levels cover TILE * TILE)");
+  const int tiles = (int)((cells + VLFB_LFB_PACK_TILE - 1) / VLFB_LFB_PACK_TILE);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(lfb_pack_tile_scan_kernel, dim3((unsigned)tiles), dim3(kPackThreads), 0, s, count, b.capacity, cells, offsets);
+  if (tiles > 1) {
+    hipLaunchKernelGGL(lfb_pack_totals_scan_kernel, dim3(1), dim3(kPackThreads), 0, s, cells, tiles, offsets);
+    hipLaunchKernelGGL(lfb_pack_add_base_kernel, dim3((unsigned)(tiles - 1)), dim3(kPackThreads), 0, s, cells, offsets);
+  }
+  return check_launch("lfb_pack_offsets");
+}
+
+extern "C" int vlfb_lfb_pack(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, const int64_t* offsets,
+                             int64_t first_row, int64_t rows, void* out, int out_dtype, int32_t* keys, vlfb_stream_t stream) {
+  BankP b;
+  int rc = check_desc(d, &b);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(bank && count && offsets && out && keys, "lfb_pack: NULL buffer");
+  VLFB_REQUIRE(dtype_ok(out_dtype), "lfb_pack: out dtype must be f32, bf16 or f16");
+  VLFB_REQUIRE((int64_t)b.n_videos * b.n_steps <= VLFB_LFB_PACK_MAX_CELLS, "lfb_pack: more than 2^20 cells (see vlfb_lfb_pack_offsets)");
+  VLFB_REQUIRE(rows >= 0 && rows < (1 << 20), "lfb_pack: rows out of range");
+  VLFB_REQUIRE(first_row >= 0, "lfb_pack: first_row is negative");
+  if (rows == 0) return VLFB_OK;
+  hipLaunchKernelGGL(lfb_pack_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, b, (const char*)bank, count,
+                     offsets, first_row, out, out_dtype, keys);
+  return check_launch("lfb_pack");
 }

@@ -127,6 +127,10 @@ class LfbDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_videos", "n_steps", "capacity", "dim", "dtype", "step_base")]
 
 
+LFB_PACK_TILE = 1024                                # vlfb.h VLFB_LFB_PACK_TILE: cells one workgroup of the offset scan covers
+LFB_PACK_MAX_CELLS = LFB_PACK_TILE * LFB_PACK_TILE  # vlfb.h VLFB_LFB_PACK_MAX_CELLS: what its two levels cover
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _SIGS = {
@@ -213,6 +217,8 @@ _SIGS = {
     "vlfb_lfb_gather_slots": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _P, _I64, C.c_int, C.c_int, _P, C.c_int, _P]),
     "vlfb_lfb_sample_compact": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, _P, C.c_int, _P]),
     "vlfb_lfb_sample_packed": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "vlfb_lfb_pack_offsets": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P]),
+    "vlfb_lfb_pack": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, _I64, _P, C.c_int, _P, _P]),
     "vlfb_topk_hits": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, C.c_int, _P, _P]),
     "vlfb_action_topk_hits": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P, C.c_int, _P, _P]),
     "vlfb_scores_merge_max": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P]),

@@ -9,7 +9,9 @@ every training iteration.
 Here the bank lives in HBM for the whole job (AVA train: 235 videos x 900 s x 16 slots x 2048 bf16
 = 13.9 GB of the 288 GB), `box_pooled` is appended to it by a kernel without leaving the device,
 and the sampled (R, K, 2048) block is written by a kernel straight into the model's `lfb` input.
-`from_reference` / `to_reference` convert to and from the reference's pickled dictionaries.
+`from_reference` / `to_reference` convert to and from the reference's pickled dictionaries.  Whatever leaves the bank
+(`to_reference`, `save`, `merge_from`) reads it through `packed_chunks`: the occupied rows only, in cell order, one staging
+chunk at a time (vlfb_lfb_pack_offsets / vlfb_lfb_pack), never a dense copy.
 
 All compute goes through libvlfb_hip.so (vlfb_lfb_*); there is no host fallback.
 """
@@ -68,6 +70,21 @@ def epic_noun_window_steps(center_frames, window, max_per_frame=10, frames_per_s
     return _ceil_div(lower, sf), upper // sf
 
 
+def reference_draw_clip(counts, video, centre, window, K, rng):
+    """the slot table of ONE `sample_lfb` call (lib/datasets/ava.py:300-323): the occupied seconds of the window around
+    `centre` (a bank step: keyframe second minus the bank's first second) in ascending order, one
+    `rng.choice(range(num_feat), min(num_feat, K), replace=False)` each -> int32 [window][K], -1 = empty slot"""
+    t = np.full((int(window), int(K)), -1, dtype=np.int32)
+    lower = int(centre) - int(window) // 2
+    for j in range(int(window)):
+        si = lower + j
+        n = int(counts[video, si]) if (0 <= video < counts.shape[0] and 0 <= si < counts.shape[1]) else 0
+        if n > 0:                                    # `if si in in_video_lfb`
+            used = min(n, int(K))
+            t[j, :used] = rng.choice(range(n), used, replace=False)
+    return t
+
+
 def reference_draw_table(counts, vid, centre, clip_index, window, K, rng):
     """The slot table of `sample_lfb` (lib/datasets/ava.py:300-323) for the rows of a minibatch, drawn from `rng` in the
     reference's call order: clips in minibatch order (ava.py:205-230 appends one sampled bank per clip; rows of one clip --
@@ -84,15 +101,7 @@ def reference_draw_table(counts, vid, centre, clip_index, window, K, rng):
     for r in range(rows):
         if prev is None or ids[r] != ids[prev]:              # a new clip of the minibatch: its own draw
             # (even when it names the same keyframe as the clip before it: still a NEW draw, as in the reference)
-            t = np.full((int(window), int(K)), -1, dtype=np.int32)
-            lower = int(centre[r]) - int(window) // 2
-            for j in range(int(window)):
-                si = lower + j
-                n = int(counts[vid[r], si]) if (0 <= vid[r] < counts.shape[0] and 0 <= si < counts.shape[1]) else 0
-                if n > 0:                                    # `if si in in_video_lfb`
-                    used = min(n, int(K))
-                    t[j, :used] = rng.choice(range(n), used, replace=False)
-            cur = t
+            cur = reference_draw_clip(counts, vid[r], centre[r], window, K, rng)
         elif vid[r] != vid[prev] or centre[r] != centre[prev]:
             raise ValueError("rows %d and %d belong to one clip but name different keyframes" % (prev, r))
         table[r] = cur
@@ -110,7 +119,8 @@ class DeviceBank(object):
                  video_ids=None):
         hip.lib()
         self.device = torch.device(device)
-        self.code = hip.BF16 if dtype in ("bf16", torch.bfloat16) else hip.F32
+        self.code = (hip.BF16 if dtype in ("bf16", torch.bfloat16) else
+                     hip.F16 if dtype in ("fp16", "f16", torch.float16) else hip.F32)
         self.desc = hip.LfbDesc(int(n_videos), int(n_steps), int(capacity), int(dim), self.code, int(step_base))
         nbytes = hip.lib().vlfb_lfb_bank_bytes(C.byref(self.desc))
         if nbytes <= 0:
@@ -378,16 +388,108 @@ class DeviceBank(object):
         bank.check_no_drops()
         return bank
 
-    def to_reference(self, frame_level=False, sample_freq=None):
-        cnt = self.counts()
-        data = self.bank.view(self.n_videos, self.n_steps, self.capacity, self.dim).float().cpu().numpy()
-        out = {}
-        for vi in range(self.n_videos):
-            key = self.video_ids[vi] if self.video_ids is not None else vi
-            out[key] = {}
-            for s in np.nonzero(cnt[vi])[0]:
+    def to_reference(self, frame_level=False, sample_freq=None, chunk_rows=65536):
+        """the reference's dictionaries, fp32: {video: {sec: [feat, ...]}} or, frame_level, {video: {frame: feat}}.  Reads the
+        bank through `packed_chunks`: the device memory it takes is one staging chunk plus the offsets, whatever the bank's size."""
+        out = {(self.video_ids[vi] if self.video_ids is not None else vi): {} for vi in range(self.n_videos)}
+        names = list(out)
+        for feats, keys, n in self.packed_chunks(chunk_rows, torch.float32):
+            f = feats[:n].cpu().numpy()
+            k = keys[:n].cpu().numpy()
+            for r in range(n):
+                steps = out[names[k[r, 0]]]
+                s = int(k[r, 1])
                 if frame_level:
-                    out[key][int(sample_freq * (s + 1) - 1)] = data[vi, s, 0].copy()
+                    steps.setdefault(int(sample_freq * (s + 1) - 1), f[r].copy())
                 else:
-                    out[key][int(s + self.step_base)] = [data[vi, s, k].copy() for k in range(cnt[vi, s])]
+                    steps.setdefault(s + self.step_base, []).append(f[r].copy())
         return out
+
+    # ---- packed export: only occupied rows move ---------------------------------------------------
+    MERGE_ROWS = 4096   # rows of one append in merge_from / load: lfb_commit_kernel is quadratic in the rows of a call
+
+    def pack_offsets(self):
+        """int64 (cells + 1,) device tensor of vlfb_lfb_pack_offsets: the packed row at which every cell starts; the last
+        entry is the number of features the bank holds"""
+        off = torch.empty(self.n_videos * self.n_steps + 1, device=self.device, dtype=torch.int64)
+        hip.call("vlfb_lfb_pack_offsets", C.byref(self.desc), hip.ptr(self.count), hip.ptr(off))
+        return off
+
+    def packed_chunks(self, chunk_rows=65536, out_dtype=None):
+        """yields (feats_dev, keys_dev, n): the bank's features in packed order (cell order, then append order), `n` rows at a
+        time in ONE staging buffer that the next step overwrites (work enqueued on the current stream before that is safe),
+        with the keys `append_enqueue` takes.  One scan, one synchronisation (the total), then one launch per chunk."""
+        chunk_rows = int(chunk_rows)
+        assert 0 < chunk_rows < (1 << 20), "packed_chunks: chunk_rows must be in (0, 2^20)"
+        off = self.pack_offsets()
+        total = int(off[-1].item())
+        dt = out_dtype or hip.TORCH_DTYPE[self.code]
+        rows = min(chunk_rows, total)
+        if rows == 0:
+            return
+        feats = torch.empty((rows, self.dim), device=self.device, dtype=dt)
+        keys = torch.empty((rows, 2), device=self.device, dtype=torch.int32)
+        for first in range(0, total, chunk_rows):
+            n = min(chunk_rows, total - first)
+            hip.call("vlfb_lfb_pack", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(off), first, n,
+                     hip.ptr(feats), hip.dtype_code(dt), hip.ptr(keys))
+            yield feats, keys, n
+
+    def merge_from(self, other):
+        """append every feature of `other` behind what this bank holds, in `other`'s order (the partial banks of two runs, or
+        of two ranks).  n_steps, dim and step_base must agree, the element type need not; banks that both carry `video_ids`
+        are matched through them, otherwise row by row.  Raises if a feature did not fit."""
+        assert (self.n_steps, self.dim, self.step_base) == (other.n_steps, other.dim, other.step_base), \
+            "merge_from: banks differ in n_steps / dim / step_base"
+        lut = None
+        if self.video_ids is not None and other.video_ids is not None:
+            missing = [v for v in other.video_ids if v not in self.video_row]
+            if missing:
+                raise hip.VlfbError("merge_from: videos %r are not in this bank" % (missing[:8],))
+            lut = self._dev_i32([self.video_row[v] for v in other.video_ids])
+        else:
+            assert self.n_videos == other.n_videos, "merge_from: banks without video_ids must have the same rows"
+        for feats, keys, n in other.packed_chunks(self.MERGE_ROWS):
+            if lut is not None:
+                keys[:n, 0] = lut[keys[:n, 0].long()]
+            self.append_enqueue(feats, keys, n)
+        self.check_no_drops()
+
+    def save(self, path):
+        """native file (.npz): the descriptor, `video_ids`, `count` and the packed rows in the bank's own element type
+        (16-bit types as uint16 bit patterns)"""
+        host =np.dtype(np.float32) if self.code == hip.F32 else np.dtype(np.uint16)
+        parts = []
+        for feats, _, n in self.packed_chunks():
+            x = feats[:n] if self.code == hip.F32 else feats[:n].view(torch.int16)
+            parts.append(x.cpu().numpy().view(host))
+        rows = np.concatenate(parts) if parts else np.zeros((0, self.dim), dtype=host)
+        fields = dict(n_videos=self.n_videos, n_steps=self.n_steps, capacity=self.capacity, dim=self.dim, dtype=self.code,
+                      step_base=self.step_base, has_video_ids=self.video_ids is not None,
+                      video_ids=np.asarray(self.video_ids if self.video_ids is not None else []),
+                      count=self.counts().astype(np.int32), rows=rows)
+        with open(path, "wb") as f:
+            np.savez(f, **fields)
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        """a bank `save` wrote: equal in `count` and, for occupied slots, in bits"""
+        with np.load(path, allow_pickle=False) as z:
+            code = int(z["dtype"])
+            ids = z["video_ids"].tolist() if bool(z["has_video_ids"]) else None
+            bank = cls(int(z["n_videos"]), int(z["n_steps"]), int(z["capacity"]), int(z["dim"]), hip.TORCH_DTYPE[code], device,
+                       int(z["step_base"]), ids)
+            count, rows = z["count"].reshape(-1), z["rows"]
+        cells = np.repeat(np.arange(count.size, dtype=np.int64), np.minimum(count, bank.capacity))
+        assert cells.size == rows.shape[0], "lfb bank file: %d rows for counts that sum to %d" % (rows.shape[0], cells.size)
+        keys = np.stack([cells // bank.n_steps, cells % bank.n_steps], axis=1).astype(np.int32)
+        held = []                                              # uploads stay alive until the appends have run
+        for first in range(0, cells.size, cls.MERGE_ROWS):
+            x = np.ascontiguousarray(rows[first:first + cls.MERGE_ROWS])
+            x = torch.from_numpy(x if code == hip.F32 else x.view(np.int16)).to(bank.device)
+            x = x if code == hip.F32 else x.view(hip.TORCH_DTYPE[code])
+            k = bank._dev_i32(keys[first:first + cls.MERGE_ROWS])
+            bank.append_enqueue(x, k, x.shape[0])
+            held.append((x, k))
+        bank.check_no_drops()
+        return bank
