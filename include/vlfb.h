@@ -730,6 +730,63 @@ int vlfb_clip_batch_preprocess_indexed(const vlfb_clip_item* items_host, const v
                                        const int32_t* store_frames_host, int dst_dtype, vlfb_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline JPEG decode on the device: the frames the reference reads with cv2.imread (lib/datasets/data_input_helper.py:51-53;
+ * written by ffmpeg -q:v 1, dataset_tools/ava/extract_ava_frames.sh:43), decoded into uint8 BGR [height][width][3] bit for
+ * bit as libjpeg-turbo does with its defaults (integer "islow" inverse DCT, "fancy" chroma upsampling).
+ *
+ * Supported: SOF0, 8-bit, one scan holding all components; one component, or Y / Cb / Cr with luma sampling 1x1, 2x1 or 2x2
+ * and chroma 1x1; 8-bit quantisation tables; Huffman table selectors 0 / 1; any restart interval.  The host parses the file
+ * (lib/datasets/jpeg.py) and only moves bytes: an item carries the raw DQT / DHT content, the kernels build their tables.
+ *
+ *   offset  0  scan          the entropy-coded bytes of the scan (stuffed zeros and restart markers included)
+ *           8  dst           uint8 BGR [height][width][3]; a grey file stores B = G = R
+ *          16  seg_offsets   uint32 [n_segments]: where each restart interval's data begins in `scan` (the first is 0, the
+ *                            others follow their RSTn marker); one entry when the file has no restart markers
+ *          24  ws_offset     where this item's part of the workspace begins: the sum of vlfb_jpeg_workspace_bytes of the
+ *                            items before it
+ *          32  scan_bytes, n_segments, width, height, n_comp, restart_interval (MCUs; 0 = none)
+ *          56  h[4], v[4]    sampling factors per component; tq[4], td[4], ta[4]: its quantisation / DC / AC table
+ *          76  reserved (0)
+ *          80  quant[4][64]  as in DQT (zigzag order)
+ *         336  huff[4][272]  DC tables 0, 1, then AC tables 0, 1; each as in DHT: 16 counts, then up to 256 symbols
+ *   sizeof = VLFB_JPEG_ITEM_BYTES = 1424, no padding.  Items of one batch may differ in every field.
+ *
+ * Three launches: entropy decode (one wave per restart interval, or per frame when there is none: the parallelism of a
+ * minibatch of ffmpeg frames is its ~256 frames) into int16 coefficients, natural order, per component in whole MCUs;
+ * dequantisation and inverse DCT into sample planes; upsampling, colour conversion and store.  Coefficients and planes live
+ * in `workspace` (16-byte aligned, vlfb_jpeg_workspace_bytes of the batch).  No byte outside [scan, scan + scan_bytes) is
+ * read and none outside dst's height * width * 3 is written, whatever the stream holds; loops are bounded by the MCU count.
+ * A missing code, a stream that ends early or a restart marker out of place stops that restart interval: its remaining
+ * coefficients are zero and the item's word of `status` (int32 [n_items], written by every call: 0 = decoded) gets
+ * VLFB_JPEG_TRUNCATED / _BAD_CODE / _BAD_RESTART bits.  Nothing synchronises with the host.
+ *
+ * `items_host` is checked before anything is launched (VLFB_ERR_ARG, the message names the item): n_items in 1..65535, sizes
+ * in 1..65535, sampling and selectors as above, non-NULL addresses, scan_bytes < 2^30, n_segments >= 1, Huffman counts that
+ * form a prefix code, ws_offset as defined above, workspace_bytes large enough.  `items_dev` is the same array in device
+ * memory, uploaded by the caller in stream order, as for vlfb_clip_batch_preprocess.
+ *
+ * vlfb_jpeg_workspace_bytes: bytes of workspace the first n_items items need (< 0 and a message for a bad item).
+ * vlfb_jpeg_decode_host: the same arithmetic (csrc/vlfb_jpeg_core.h, compiled for the host) for ONE item whose scan and
+ * seg_offsets are HOST addresses; single-threaded, allocates its own workspace, needs no GPU.  It is the checker that pins
+ * the arithmetic against libjpeg-turbo where no GPU is present, not a loader path.
+ * ------------------------------------------------------------------------------------------ */
+#define VLFB_JPEG_ITEM_BYTES 1424
+enum { VLFB_JPEG_TRUNCATED = 1, VLFB_JPEG_BAD_CODE = 2, VLFB_JPEG_BAD_RESTART = 4 };
+typedef struct vlfb_jpeg_item {
+  uint64_t scan, dst, seg_offsets, ws_offset;
+  uint32_t scan_bytes, n_segments;
+  int32_t  width, height, n_comp, restart_interval;
+  uint8_t  h[4], v[4], tq[4], td[4], ta[4];
+  uint8_t  reserved[4];
+  uint8_t  quant[4][64];
+  uint8_t  huff[4][272];
+} vlfb_jpeg_item;
+int64_t vlfb_jpeg_workspace_bytes(const vlfb_jpeg_item* items_host, int n_items);
+int vlfb_jpeg_decode_batch(const vlfb_jpeg_item* items_host, const vlfb_jpeg_item* items_dev, int n_items, void* workspace,
+                           int64_t workspace_bytes, int32_t* status_dev, vlfb_stream_t stream);
+int vlfb_jpeg_decode_host(const vlfb_jpeg_item* item, uint8_t* dst, int32_t* status);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluation metrics on the device.  Replace the host meter of lib/utils/metrics.py, which fetches `pred` and
  * `labels` from every GPU every iteration (get_multi_gpu_outputs, :514-540), and tools/evaluate_actions.py.
  * All state (counters, cursor, tables) is caller-owned device memory; every count is an integer and the two

@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--dtype", default="mix")
     ap.add_argument("--src", type=int, nargs=2, default=[256, 340])
     ap.add_argument("--color", action="store_true", help="TRAIN.USE_COLOR_AUGMENTATION")
+    ap.add_argument("--jpeg", action="store_true", help="(c) reads its clips from a FrameStore fed JPEG bytes (fetch_jpeg), every "
+                    "frame new every step: the frames are decoded on the loader's stream (tools/jpeg_decode_profile.py makes them)")
+    ap.add_argument("--target-bytes", type=int, default=55000, help="--jpeg: mean file size the quality is chosen for")
     args = ap.parse_args()
 
     import torch
@@ -108,10 +111,20 @@ def main():
             submit_s.append(time.perf_counter() - t0)
     loader.submit = timed_submit
 
+    store = None
+    if args.jpeg:
+        from datasets.frame_store import FrameStore
+        from jpeg_decode_profile import make_frames
+        files, _, quality = make_frames(N * T, H, W, args.target_bytes)
+        store = FrameStore(H, W, 2 * N * T, loader.device, loader.stream)
+        store.fetch_jpeg = lambda v, f: files[(v * T + f) % (N * T)]
+
     def source():
         k = 0
         while True:
-            yield (videos, boxes01, [labels[n * PER:(n + 1) * PER] for n in range(N)],
+            # --jpeg: clip n of step k is frames k * T .. of video n, none of them resident
+            clips = videos if store is None else [(store, n, list(range(k * T, (k + 1) * T))) for n in range(N)]
+            yield (clips, boxes01, [labels[n * PER:(n + 1) * PER] for n in range(N)],
                    dict(iteration=k, videos=list(range(N)), secs=list(secs)), np.random.RandomState(k))
             k += 1
 
@@ -167,8 +180,15 @@ def main():
     print("%-8s %s   median      min      max   (ms per step)" % ("feed", " ".join("%8s" % ("rep%d" % r) for r in range(args.repeats))))
     for name, v in ms.items():
         print("%-8s %s %8.3f %8.3f %8.3f" % (name, " ".join("%8.3f" % x for x in v), float(np.median(v)), min(v), max(v)))
-    print("loader: host time of one submit() %.2f ms (mean of %d), %.1f MB of frames per minibatch through pinned memory"
-          % (1e3 * float(np.mean(submit_s)), len(submit_s), N * T * H * W * 3 / 1e6))
+    if store is None:
+        print("loader: host time of one submit() %.2f ms (mean of %d), %.1f MB of frames per minibatch through pinned memory"
+              % (1e3 * float(np.mean(submit_s)), len(submit_s), N * T * H * W * 3 / 1e6))
+    else:
+        store.check_decoded()
+        print("loader: host time of one submit() %.2f ms (mean of %d): %d JPEG files of mean %d bytes (PIL quality %d) parsed, copied "
+              "into the pinned ring and decoded on the loader's stream; %.1f MB per minibatch through pinned memory"
+              % (1e3 * float(np.mean(submit_s)), len(submit_s), N * T, int(np.mean([len(f) for f in files])), quality,
+                 store.uploaded_bytes / max(store.fetched, 1) * N * T / 1e6))
     print("idle device, per minibatch: loader stream %.3f ms (H2D copies + launches + bank sample), deliver %.3f ms "
           "(device-to-device copies of %.0f MB on the training stream); medians of 5"
           % (float(np.median(dev_ms["loader stream"])), float(np.median(dev_ms["deliver"])),

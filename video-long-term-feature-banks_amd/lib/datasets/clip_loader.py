@@ -111,6 +111,7 @@ class ClipSlots(object):
             s.consumed = torch.cuda.Event()
             self.slots.append(s)
         self.stream = torch.cuda.Stream(device=dev)
+        self._ordered = False          # the stream has not yet been put behind the fills that zeroed the slots' buffers
         self._next_slot = 0
         self._lock = threading.Lock()
         self._thread = None
@@ -125,6 +126,11 @@ class ClipSlots(object):
             s.state = "filling"
             self._next_slot = (self._next_slot + 1) % len(self.slots)
         try:
+            if not self._ordered:
+                # the slots' device buffers (this class's and the subclass's) were zeroed by fills on the device's default
+                # stream, which this stream does not follow by itself: a fill that runs late would wipe the first minibatch
+                self.stream.wait_stream(torch.cuda.default_stream(self.device))
+                self._ordered = True
             s.serial += 1
             s.stores = []
             if s.used_h2d:

@@ -123,6 +123,21 @@ CLIP_ITEM_BYTES = 176                                               # vlfb.h VLF
 assert C.sizeof(ClipItem) == CLIP_ITEM_BYTES
 
 
+class JpegItem(C.Structure):
+    """vlfb.h vlfb_jpeg_item: one baseline JPEG frame for vlfb_jpeg_decode_batch (device addresses) / vlfb_jpeg_decode_host
+    (host addresses); datasets.jpeg.JpegInfo.fill writes everything but the addresses"""
+    _fields_ = [(n, C.c_uint64) for n in ("scan", "dst", "seg_offsets", "ws_offset")] + \
+               [("scan_bytes", C.c_uint32), ("n_segments", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("width", "height", "n_comp", "restart_interval")] + \
+               [(n, C.c_uint8 * 4) for n in ("h", "v", "tq", "td", "ta", "reserved")] + \
+               [("quant", C.c_uint8 * 64 * 4), ("huff", C.c_uint8 * 272 * 4)]
+
+
+JPEG_ITEM_BYTES = 1424                                              # vlfb.h VLFB_JPEG_ITEM_BYTES
+assert C.sizeof(JpegItem) == JPEG_ITEM_BYTES
+JPEG_TRUNCATED, JPEG_BAD_CODE, JPEG_BAD_RESTART = 1, 2, 4           # bits of a vlfb_jpeg_decode_batch status word
+
+
 class LfbDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_videos", "n_steps", "capacity", "dim", "dtype", "step_base")]
 
@@ -210,6 +225,9 @@ _SIGS = {
     "vlfb_clip_batch_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "vlfb_clip_batch_channel_sums_indexed": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
     "vlfb_clip_batch_preprocess_indexed": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P]),
+    "vlfb_jpeg_workspace_bytes": (_I64, [_P, C.c_int]),
+    "vlfb_jpeg_decode_batch": (C.c_int, [_P, _P, C.c_int, _P, _I64, _P, _P]),
+    "vlfb_jpeg_decode_host": (C.c_int, [_P, _P, _P]),
     "vlfb_lfb_bank_bytes": (_I64, [C.POINTER(LfbDesc)]),
     "vlfb_lfb_append": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, C.c_int, _P, _I64, _P, _P]),
     "vlfb_lfb_sample_window": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, C.c_uint64,

@@ -38,7 +38,8 @@ def build_ava_bank(engine, loader, index, store, bank, rng=None):
     """the loop of tools/lfb_loader.py:200-223 for AVA: `engine` an lfb_infer_only engine planned in test mode, `loader` its
     MinibatchLoader, `index` an lfb_infer_only datasets.ava.AvaIndex, `store` the FrameStore (on the loader's stream) whose
     `fetch` decodes, `bank` a DeviceBank whose rows are the index's video indices.  Per batch: next / deliver / forward /
-    append_enqueue(box_pooled); nothing in the loop waits for the device, one synchronisation and check_no_drops at the end.
+    append_enqueue(box_pooled); nothing in the loop waits for the device, one synchronisation, check_no_drops and the store's
+    check_decoded at the end.
 
     One deviation from the reference: the clips that pad its last short batch (indices.append(indices[0])) are run and
     APPENDED again there, so that keyframe's boxes are twice in its pickle.  Here their rows get video -1 and are skipped."""
@@ -68,6 +69,7 @@ def build_ava_bank(engine, loader, index, store, bank, rng=None):
         loader.stop()
     torch.cuda.current_stream().synchronize()
     bank.check_no_drops()
+    store.check_decoded()                             # frames the store decoded from JPEG bytes: none was damaged
     return bank
 
 
