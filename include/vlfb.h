@@ -873,6 +873,36 @@ int vlfb_ava_match_tp(const float* scores, const double* det_box, int64_t n_rows
 int vlfb_class_ap_voc(const float* scores, const uint8_t* tp, const int32_t* n_gt, int64_t n, int64_t cols, double* ap,
                       void* workspace, int64_t workspace_bytes, int flags, vlfb_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * AVA multi-crop merge: the last stage of the reference's multi-crop test (tools/test_net.py:57-87 runs scales x 2 flips x 3
+ * spatial shifts; lib/utils/metrics.py:599-711 merges their csv files).  One call merges the three shifts of ONE (scale,
+ * flip) and accumulates the result; it restates metrics.py:654-677 and :703-705 on arrays, in fp64 and in the reference's
+ * operation order, so that every decision is the reference's.
+ *
+ * logits: the `pred` rows of shift 0, 1, 2: shift s begins at element s * shift_stride, row r ld elements further on,
+ * cols <= ld.  `dtype` is VLFB_F32 / VLFB_F16 / VLFB_BF16 (what an engine's `pred` holds; converted to fp64 exactly) or
+ * VLFB_F64, which only this entry point takes: logits parsed from score files, as the reference merges them.  boxes fp64 [rows][4] = (x1, y1, x2, y2) normalised to the ORIGINAL frame;
+ * frame_hw int32 [rows][2] = (height, width) of the row's source frames.  Per row:
+ *   w = (double)(width * scale) / height;  nc = (double)min(scale, max_crop) / w
+ *   center_left = 0.5 - nc / 2.0, center_right = 0.5 + nc / 2.0, lcrop_right = nc, rcrop_left = 1.0 - nc
+ *   with `flip`: x1' = 1.0 - x2, x2' = 1.0 - x1
+ *   shift 1 (centre) sees the box iff x2 > center_left && x1 < center_right; shift 0 (left) iff x1 < lcrop_right;
+ *   shift 2 (right) iff x2 > rcrop_left -- all strict
+ *   combined = (sum over the shifts that see the box, in shift order 0, 1, 2, of 1 / (1 + exp(-logit))) / their number
+ * (the reference adds the centre first; fp64 addition is commutative and the third term is last either way, so the sums are
+ * the same bits).  A box no shift sees gives NaN, like np.mean([]); logits of a shift that does not see the box are not read.
+ * acc fp64 [rows][cols] becomes combined when `first` is set, else acc + combined: over the calls of a keyframe in merge
+ * order (scale, then flip) that is the reference's sequential np.sum.  out32 (may be NULL) gets (float)acc after the update;
+ * valid (may be NULL) uint8 [rows] gets the mask of the shifts that see the box (bit s = shift s), written by one thread
+ * per row.  No atomics: every output element has one writer.
+ * VLFB_ERR_ARG before anything is launched: a NULL logits / boxes / frame_hw / acc, cols < 1, rows < 0, ld < cols,
+ * scale < 1, max_crop < 1, an unknown dtype.  rows == 0 succeeds and launches nothing.  frame_hw is device memory the host
+ * cannot check: a height of 0 gives NaN / inf geometry, never an access outside the arrays. */
+enum { VLFB_F64 = 11 };
+int vlfb_multicrop_merge(const void* logits, int dtype, int64_t shift_stride, int64_t ld, const double* boxes,
+                         const int32_t* frame_hw, int64_t rows, int64_t cols, int scale, int max_crop, int flip, int first,
+                         double* acc, float* out32, uint8_t* valid, vlfb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

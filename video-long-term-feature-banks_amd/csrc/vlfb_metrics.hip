@@ -1,6 +1,7 @@
 // Evaluation metrics on the device (include/vlfb.h, "Evaluation metrics"): top-k hit counters, the clip-merge score
-// table, per-class average precision / ROC-AUC, EPIC action top-k.  Replaces the host meter of the reference's
-// lib/utils/metrics.py and tools/evaluate_actions.py, which fetches `pred` and `labels` every iteration.
+// table, per-class average precision / ROC-AUC, EPIC action top-k, AVA frame-mAP and the AVA multi-crop merge.  Replaces
+// the host meter of the reference's lib/utils/metrics.py and tools/evaluate_actions.py, which fetches `pred` and `labels`
+// every iteration.
 //
 // Determinism: every count is an integer (exact, order-independent); the only floating-point sums (AP, AUC) are taken
 // over a fixed partition of the sorted column (AP_THREADS chunks of npad / AP_THREADS elements, then a fixed tree), the
@@ -618,4 +619,85 @@ extern "C" int vlfb_class_ap_voc(const float* scores, const uint8_t* tp, const i
   class_ap_voc_global_kernel<<<(unsigned)cols, AP_THREADS, 0, s>>>(scores, tp, n_gt, (int)n, (int)cols, npad,
                                                                   static_cast<unsigned long long*>(workspace), ap);
   return check_launch("class_ap_voc");
+}
+
+// ---- AVA multi-crop merge (include/vlfb.h, "AVA multi-crop merge"): the three spatial shifts of one (scale, flip) ---------
+namespace vlfb {
+
+constexpr int MC_THREADS = 256;
+constexpr long long MC_MAX_BLOCKS = 1 << 16;
+
+// a logit as fp64: exact for every element type (fp64 logits are the ones parsed from score files)
+template <typename T> __device__ __forceinline__ double mc_logit(const T* p) { return (double)Elem<T>::ld(p); }
+template <> __device__ __forceinline__ double mc_logit<double>(const double* p) { return *p; }
+
+// A thread owns one (row, class) element; the row's geometry is a handful of fp64 operations and is formed again by every
+// thread of the row, so that no thread waits for another.  The thread of class 0 writes the row's mask.
+template <typename T>
+__global__ __launch_bounds__(MC_THREADS) void multicrop_merge_kernel(const T* __restrict__ logits, long long shift_stride, long long ld,
+                                                                     const double* __restrict__ boxes, const int32_t* __restrict__ frame_hw,
+                                                                     long long rows, int cols, int scale, int max_crop, int flip, int first,
+                                                                     double* __restrict__ acc, float* __restrict__ out32,
+                                                                     uint8_t* __restrict__ valid) {
+  const long long n = rows * cols;
+  for (long long i = (long long)blockIdx.x * MC_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * MC_THREADS) {
+    const long long r = i / cols;
+    const int c = (int)(i - r * cols);
+    const long long height = frame_hw[2 * r], width = frame_hw[2 * r + 1];
+    const double w = (double)(width * scale) / (double)height;
+    const double nc = (double)(scale < max_crop ? scale : max_crop) / w;
+    const double center_left = 0.5 - nc / 2.0, center_right = 0.5 + nc / 2.0;
+    const double lcrop_right = nc, rcrop_left = 1.0 - nc;
+    double x1 = boxes[4 * r], x2 = boxes[4 * r + 2];
+    if (flip) {
+      const double a = 1.0 - x2, b = 1.0 - x1;
+      x1 = a;
+      x2 = b;
+    }
+    const bool v[3] = {x1 < lcrop_right, x2 > center_left && x1 < center_right, x2 > rcrop_left};
+    double sum = 0.0;
+    int nv = 0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+      if (v[s]) {                                                 // (a shift that does not see the box is not read)
+        const double x = mc_logit<T>(logits + s * shift_stride + r * ld + c);
+        sum += 1.0 / (1.0 + exp(-x));
+        ++nv;
+      }
+    const double combined = sum / (double)nv;                     // 0 / 0 = NaN for a box no crop sees, like np.mean([])
+    const double a = first ? combined : acc[i] + combined;
+    acc[i] = a;
+    if (out32) out32[i] = (float)a;
+    if (valid && c == 0) valid[r] = (uint8_t)((v[0] ? 1 : 0) | (v[1] ? 2 : 0) | (v[2] ? 4 : 0));
+  }
+}
+
+}  // namespace vlfb
+
+extern "C" int vlfb_multicrop_merge(const void* logits, int dtype, int64_t shift_stride, int64_t ld, const double* boxes,
+                                    const int32_t* frame_hw, int64_t rows, int64_t cols, int scale, int max_crop, int flip, int first,
+                                    double* acc, float* out32, uint8_t* valid, vlfb_stream_t stream) {
+  VLFB_REQUIRE(dtype_ok(dtype) || dtype == VLFB_F64, "multicrop_merge: unknown dtype %d", dtype);
+  VLFB_REQUIRE(rows >= 0 && rows < (1ll << 31), "multicrop_merge: bad rows %lld", (long long)rows);
+  VLFB_REQUIRE(cols >= 1 && cols < (1ll << 31), "multicrop_merge: bad cols %lld", (long long)cols);
+  VLFB_REQUIRE(ld >= cols, "multicrop_merge: ld = %lld is less than cols = %lld", (long long)ld, (long long)cols);
+  VLFB_REQUIRE(shift_stride >= 0, "multicrop_merge: negative shift_stride %lld", (long long)shift_stride);
+  VLFB_REQUIRE(scale >= 1, "multicrop_merge: scale must be positive, got %d", scale);
+  VLFB_REQUIRE(max_crop >= 1, "multicrop_merge: max_crop must be positive, got %d", max_crop);
+  VLFB_REQUIRE(logits != nullptr, "multicrop_merge: logits is required");
+  VLFB_REQUIRE(boxes != nullptr, "multicrop_merge: boxes is required");
+  VLFB_REQUIRE(frame_hw != nullptr, "multicrop_merge: frame_hw is required");
+  VLFB_REQUIRE(acc != nullptr, "multicrop_merge: acc is required");
+  if (rows == 0) return VLFB_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long n = (long long)rows * cols;
+  const unsigned grid = (unsigned)std::min<long long>((n + MC_THREADS - 1) / MC_THREADS, MC_MAX_BLOCKS);
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    multicrop_merge_kernel<T><<<grid, MC_THREADS, 0, s>>>(static_cast<const T*>(logits), shift_stride, ld, boxes, frame_hw, rows, (int)cols,
+                                                          scale, max_crop, flip ? 1 : 0, first ? 1 : 0, acc, out32, valid);
+  };
+  if (dtype == VLFB_F64) launch(double{});
+  else with_elem(dtype, launch);
+  return check_launch("multicrop_merge");
 }

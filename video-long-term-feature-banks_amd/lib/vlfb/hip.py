@@ -16,6 +16,7 @@ MIX, MIX_W2 = 4, 5                                  # ... of the "mix" path (spl
 MIXH, MIXH_W2 = 6, 7                                # ... of the two-plane fp16 forward (two-term fp16 FPROP copy; DGRAD as MIX / MIX_W2)
 MIX_W2I, MIXH_W2I = 9, 10                           # ... with the two-term DGRAD copy interleaved per 64-channel k-tile (MATH_F16W2)
 F16PAIR = 8                                         # two-plane fp16 tensors (vlfb.h VLFB_F16PAIR; pool descriptors)
+F64 = 11                                            # fp64 logits (vlfb.h VLFB_F64; vlfb_multicrop_merge only)
 MIX_W2_SCALE = 1024.0                               # vlfb.h VLFB_MIX_W2_SCALE
 MATH_NATIVE, MATH_BF16X3, MATH_BF16X6, MATH_F16X3 = 0, 3, 6, 13     # vlfb_conv_desc.math
 MATH_F16W2 = 12                                     # ... 16-bit DGRAD on two-term weights interleaved per k-tile (MIX_W2I)
@@ -243,6 +244,8 @@ _SIGS = {
     "vlfb_class_ap_auc": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _I64, C.c_int, _P]),
     "vlfb_ava_match_tp": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "vlfb_class_ap_voc": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _I64, C.c_int, _P]),
+    "vlfb_multicrop_merge": (C.c_int, [_P, C.c_int, _I64, _I64, _P, _P, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
