@@ -371,8 +371,10 @@ int vlfb_softmax_bwd_p32(const float* dp, const float* p, void* ds, int ds_dtype
  *   fwd:  prob[b][l1][l2] = softmax_l2(scale * sum_c theta[b][l1][c] * phi[b][l2][c])
  *   bwd:  ds[b][l1][l2]   = scale * prob o (dP - sum_l2(dP o prob)),  dP = sum_c dy[b][l1][c] * g[b][l2][c]
  * operands / outputs are `dtype` (16-bit types only), row-major as indexed above.  Supported shapes:
- * 512 <= l2 <= 1024 with l2 % 8 == 0, ci % 64 == 0; otherwise VLFB_ERR_UNSUPPORTED and the caller composes
- * vlfb_conv_run + vlfb_softmax_*.  vlfb_attn_scores_supported returns 0 or a mask of the flags below: whether the
+ * 512 <= l2 <= 1024 with l2 % 8 == 0, 64 <= ci <= 1024 with ci % 64 == 0, l1 >= 64, and l1 * ci < 2^30 and
+ * l1 * l2 < 2^30 (32-bit element offsets inside one batch entry); otherwise VLFB_ERR_UNSUPPORTED and the caller
+ * composes vlfb_conv_run + vlfb_softmax_*.  scale must be > 0 (a kernel takes the row maximum before scaling); any
+ * other value is VLFB_ERR_ARG.  Both refusals come back before anything is launched.  vlfb_attn_scores_supported returns 0 or a mask of the flags below: whether the
  * shape can run at all, and for which direction the fused kernel was MEASURED faster than the composed one on
  * MI355X (the engine fuses a direction only then). */
 enum { VLFB_ATTN_CAN_RUN = 1, VLFB_ATTN_FWD_FASTER = 2, VLFB_ATTN_BWD_FASTER = 4 };
