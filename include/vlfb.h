@@ -605,6 +605,14 @@ int vlfb_lfb_pack_offsets(const vlfb_lfb_desc* d, const int32_t* count, int64_t*
  * call as for vlfb_lfb_append, first_row >= 0. */
 int vlfb_lfb_pack(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, const int64_t* offsets,
                   int64_t first_row, int64_t rows, void* out, int out_dtype, int32_t* keys, vlfb_stream_t stream);
+/* Non-finite rows of a finished bank, counted where the bank lives (an inference pass has no loss to guard it: on the
+ * 16-bit paths an activation above the format's range becomes Inf or NaN silently, and such a row poisons every training
+ * step that samples it).  An occupied row is slot < min(count[cell], capacity) of a cell.  ADDS into out[0] the number of
+ * occupied rows with at least one NaN or +-Inf element and into out[1] the number of occupied rows examined (int64 [2]
+ * in device memory, caller-zeroed).  Unoccupied slots are not read.  Integer adds only: the result does not depend on the
+ * launch geometry.  Rows whose byte length and address are multiples of 16 are read with 16-byte loads. */
+int vlfb_lfb_count_nonfinite(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, int64_t* out /* [2] */,
+                             vlfb_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Clip preprocessing on the device.  Replaces the per-frame cv2 / NumPy chain of
@@ -802,6 +810,18 @@ int vlfb_jpeg_decode_host(const vlfb_jpeg_item* item, uint8_t* dst, int32_t* sta
  * sort is not stable: ties are pinned by this rule.) */
 int vlfb_topk_hits(const void* scores, int dtype, const int32_t* labels, int64_t rows, int64_t cols, const int32_t* ks,
                    int nk, int64_t* hits, vlfb_stream_t stream);
+/* vlfb_topk_hits that also KEEPS the rows (all_preds.append / stack_predictions, metrics.py:147-163, 384-388, whose table
+ * finalize_metrics writes as epic_predictions_<name>.pkl, :222-226), in the same single launch.  `hits` gets exactly what
+ * vlfb_topk_hits adds for the same arguments: every row of the call is counted, the padding rows of the last batch
+ * included, as the reference's running error counts them.  Row r of the call is stored at row *cursor + r of table fp32
+ * [total_rows][cols] (the scores converted to fp32, which is exact) and table_labels int32 [total_rows] (the label as it
+ * is, out of range or not) when that row is < total_rows; rows at stream positions >= total_rows are dropped and nothing
+ * outside the two tables is written.  `cursor` is an int64 IN DEVICE MEMORY that the call reads and then advances by
+ * `rows`, as in vlfb_scores_merge_max: with all other arguments constant the call can sit in a replayed call list or a
+ * captured graph.  total_rows >= 1. */
+int vlfb_topk_hits_keep(const void* scores, int dtype, const int32_t* labels, int64_t rows, int64_t cols, const int32_t* ks,
+                        int nk, int64_t* hits, float* table, int32_t* table_labels, int64_t total_rows, int64_t* cursor,
+                        vlfb_stream_t stream);
 /* EPIC action top-k (compute_top_k_actions, evaluate_actions.py:77-98): the same rank rule over the flattened index
  * v * Nn + n of (verb[r][v] * noun[r][n]) * prior[v][n], each product rounded to fp32 in that order; prior may be NULL.
  * A row with either label out of range is skipped. */

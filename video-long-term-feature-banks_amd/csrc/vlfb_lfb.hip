@@ -302,6 +302,59 @@ __global__ void lfb_pack_kernel(BankP b, const char* __restrict__ bank, const in
   }
 }
 
+// ---- non-finite rows ---------------------------------------------------------------------------------------------------
+// a wave per row g = cell * capacity + slot (grid-stride); rows of unoccupied slots are not loaded.  An element is NaN or
+// +-Inf iff its exponent field is all ones; a 32-bit word of a 16-bit bank holds two elements.
+constexpr int kFiniteThreads = 256;
+constexpr int kFiniteMaxBlocks = 4096;
+
+__device__ __forceinline__ bool word_nonfinite(uint32_t w, int dtype) {
+  if (dtype == VLFB_F32) return (w & 0x7f800000u) == 0x7f800000u;
+  const uint32_t e = dtype == VLFB_F16 ? 0x7c00u : 0x7f80u;
+  return (w & e) == e || ((w >> 16) & e) == e;
+}
+
+__global__ void __launch_bounds__(kFiniteThreads)
+lfb_count_nonfinite_kernel(BankP b, const char* __restrict__ bank, const int32_t* __restrict__ count, int vec16,
+                           unsigned long long* out) {
+  __shared__ int part[kFiniteThreads / 64][2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long rows = (long long)b.n_videos * b.n_steps * b.capacity;
+  const long long row_bytes = (long long)b.dim * esize(b.dtype);
+  int bad_rows = 0, occupied = 0;                                  // (wave-uniform)
+  for (long long g = (long long)blockIdx.x * (kFiniteThreads / 64) + wave; g < rows; g += (long long)gridDim.x * (kFiniteThreads / 64)) {
+    const long long cell = g / b.capacity;
+    const int slot = (int)(g - cell * b.capacity);
+    int n = count[cell];
+    n = n < b.capacity ? n : b.capacity;
+    if (slot >= n) continue;
+    const char* row = bank + g * row_bytes;
+    bool bad = false;
+    if (vec16) {
+      const uint4* v = reinterpret_cast<const uint4*>(row);
+      for (int i = lane; i < row_bytes / 16; i += 64) {
+        const uint4 q = v[i];
+        bad |= word_nonfinite(q.x, b.dtype) | word_nonfinite(q.y, b.dtype) | word_nonfinite(q.z, b.dtype) | word_nonfinite(q.w, b.dtype);
+      }
+    } else if (b.dtype == VLFB_F32) {
+      const uint32_t* v = reinterpret_cast<const uint32_t*>(row);
+      for (int i = lane; i < b.dim; i += 64) bad |= word_nonfinite(v[i], VLFB_F32);
+    } else {
+      const unsigned short* v = reinterpret_cast<const unsigned short*>(row);
+      for (int i = lane; i < b.dim; i += 64) bad |= word_nonfinite(v[i], b.dtype);    // (the upper half of the word is 0: finite)
+    }
+    bad_rows += __any(bad) ? 1 : 0;
+    occupied += 1;
+  }
+  if (lane == 0) { part[wave][0] = bad_rows; part[wave][1] = occupied; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    int s = 0;
+    for (int w = 0; w < kFiniteThreads / 64; ++w) s += part[w][threadIdx.x];
+    if (s) atomicAdd(out + threadIdx.x, (unsigned long long)s);
+  }
+}
+
 int check_desc(const vlfb_lfb_desc* d, BankP* b) {
   VLFB_REQUIRE(d != nullptr, "lfb: descriptor is NULL");
   VLFB_REQUIRE(d->n_videos > 0 && d->n_steps > 0 && d->capacity > 0 && d->dim > 0, "lfb: empty bank geometry");
@@ -424,4 +477,20 @@ extern "C" int vlfb_lfb_pack(const vlfb_lfb_desc* d, const void* bank, const int
   hipLaunchKernelGGL(lfb_pack_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, b, (const char*)bank, count,
                      offsets, first_row, out, out_dtype, keys);
   return check_launch("lfb_pack");
+}
+
+extern "C" int vlfb_lfb_count_nonfinite(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, int64_t* out,
+                                        vlfb_stream_t stream) {
+  BankP b;
+  int rc = check_desc(d, &b);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(bank && count && out, "lfb_count_nonfinite: NULL buffer");
+  const int64_t rows = (int64_t)b.n_videos * b.n_steps * b.capacity;
+  const int64_t row_bytes = (int64_t)b.dim * (b.dtype == VLFB_F32 ? 4 : 2);
+  const int vec16 = (row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(bank) & 15) == 0;
+  const int64_t blocks = (rows + kFiniteThreads / 64 - 1) / (kFiniteThreads / 64);
+  hipLaunchKernelGGL(lfb_count_nonfinite_kernel, dim3((unsigned)(blocks < kFiniteMaxBlocks ? blocks : kFiniteMaxBlocks)),
+                     dim3(kFiniteThreads), 0, (hipStream_t)stream, b, (const char*)bank, count, vec16,
+                     reinterpret_cast<unsigned long long*>(out));
+  return check_launch("lfb_count_nonfinite");
 }

@@ -24,17 +24,30 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 // ---- top-k hits: ONE workgroup, a wave per row; the adds into `hits` are plain int64 adds of one thread ---------------
+// KEEP (vlfb_topk_hits_keep): the wave also stores its row as fp32, with the label, at table row *cursor + r when that is
+// inside the table; every thread reads the cursor before the barrier below and one thread advances it behind it.
 constexpr int TOPK_WAVES = 4;
-template <typename T>
+template <typename T, bool KEEP>
 __global__ __launch_bounds__(TOPK_WAVES * 64) void topk_hits_kernel(const T* __restrict__ scores, const int32_t* __restrict__ labels,
-                                                                    int rows, int cols, TopK ks, int64_t* __restrict__ hits) {
+                                                                    int rows, int cols, TopK ks, int64_t* __restrict__ hits,
+                                                                    float* __restrict__ table, int32_t* __restrict__ tlab,
+                                                                    long long total, long long* cursor) {
   __shared__ int part[TOPK_WAVES][MAX_K + 1];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long cur = KEEP ? *cursor : 0;
   int mine[MAX_K + 1] = {0, 0, 0, 0, 0};
   for (int r = wave; r < rows; r += TOPK_WAVES) {
     const int jl = labels[r];
-    if (jl < 0 || jl >= cols) continue;                       // (wave-uniform)
     const T* row = scores + (size_t)r * cols;
+    if (KEEP) {
+      const long long pos = cur + r;
+      if (pos >= 0 && pos < total) {                          // (wave-uniform) rows behind the end of the data set are dropped
+        float* dst = table + (size_t)pos * cols;
+        for (int j = lane; j < cols; j += 64) dst[j] = Elem<T>::ld(row + j);
+        if (lane == 0) tlab[pos] = jl;
+      }
+    }
+    if (jl < 0 || jl >= cols) continue;                       // (wave-uniform)
     const float sl = Elem<T>::ld(row + jl);
     int rank = 0;
     for (int j = lane; j < cols; j += 64) rank += outranks(Elem<T>::ld(row + j), j, sl, jl);
@@ -53,6 +66,7 @@ __global__ __launch_bounds__(TOPK_WAVES * 64) void topk_hits_kernel(const T* __r
     for (int w = 0; w < TOPK_WAVES; ++w) s += part[w][i];
     hits[threadIdx.x] += s;
   }
+  if (KEEP && threadIdx.x == 0) *cursor = cur + rows;
 }
 
 // ---- EPIC action top-k: a workgroup per row over the V x Nn products; integer atomic adds into `hits` -----------------
@@ -283,9 +297,33 @@ extern "C" int vlfb_topk_hits(const void* scores, int dtype, const int32_t* labe
   hipStream_t s = static_cast<hipStream_t>(stream);
   with_elem(dtype, [&](auto t) {
     using T = decltype(t);
-    topk_hits_kernel<T><<<1, TOPK_WAVES * 64, 0, s>>>(static_cast<const T*>(scores), labels, (int)rows, (int)cols, tk, hits);
+    topk_hits_kernel<T, false><<<1, TOPK_WAVES * 64, 0, s>>>(static_cast<const T*>(scores), labels, (int)rows, (int)cols, tk, hits,
+                                                             nullptr, nullptr, 0, nullptr);
   });
   return check_launch("topk_hits");
+}
+
+extern "C" int vlfb_topk_hits_keep(const void* scores, int dtype, const int32_t* labels, int64_t rows, int64_t cols, const int32_t* ks,
+                                   int nk, int64_t* hits, float* table, int32_t* table_labels, int64_t total_rows, int64_t* cursor,
+                                   vlfb_stream_t stream) {
+  VLFB_REQUIRE(dtype_ok(dtype), "topk_hits_keep: unknown dtype %d", dtype);
+  VLFB_REQUIRE(rows >= 0 && cols >= 1 && rows < (1ll << 31) && cols < (1ll << 31), "topk_hits_keep: bad rows / cols %lld x %lld",
+               (long long)rows, (long long)cols);
+  TopK tk;
+  if (int rc = check_ks("topk_hits_keep", ks, nk, cols, &tk)) return rc;
+  VLFB_REQUIRE(hits != nullptr, "topk_hits_keep: hits is required");
+  VLFB_REQUIRE(table != nullptr && table_labels != nullptr, "topk_hits_keep: table and table_labels are required");
+  VLFB_REQUIRE(cursor != nullptr, "topk_hits_keep: cursor is required");
+  VLFB_REQUIRE(total_rows >= 1, "topk_hits_keep: total_rows must be positive, got %lld", (long long)total_rows);
+  if (rows == 0) return VLFB_OK;
+  VLFB_REQUIRE(scores != nullptr && labels != nullptr, "topk_hits_keep: scores and labels are required");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  with_elem(dtype, [&](auto t) {
+    using T = decltype(t);
+    topk_hits_kernel<T, true><<<1, TOPK_WAVES * 64, 0, s>>>(static_cast<const T*>(scores), labels, (int)rows, (int)cols, tk, hits, table,
+                                                            table_labels, total_rows, reinterpret_cast<long long*>(cursor));
+  });
+  return check_launch("topk_hits_keep");
 }
 
 extern "C" int vlfb_action_topk_hits(const float* verb, const float* noun, const float* prior, const int32_t* verb_labels,

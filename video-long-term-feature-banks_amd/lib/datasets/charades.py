@@ -5,6 +5,7 @@ lib/datasets/charades.py and construct_label_array of charades_data_input.py).
 file or the bank; the pixels and the bank window are the clip loader's (datasets.clip_loader.FrameLoader).  Random draws
 take an explicit `rng` with the interface of Python's `random` module (the reference calls `random.randint`)."""
 import collections
+import os
 import random
 
 import numpy as np
@@ -70,6 +71,19 @@ class CharadesIndex(object):
         self.seq_len = self.video_length * self.sample_rate
         self.num_test_clips = cfg.CHARADES.get("NUM_TEST_CLIPS", cfg.CHARADES.NUM_TEST_CLIPS_DURING_TRAINING)
         self.num_test_segments = self.num_test_clips // 3     # 3-crop testing: 30 clips = 3 crops x 10 segments
+
+    @classmethod
+    def from_cfg(cls, split, lfb_infer_only, get_train_lfb=False):
+        """the index of the frame lists CharadesDataset._get_data reads (CHARADES.FRAME_LIST_DIR): TRAIN_LISTS for split
+        'train' or a train-bank pass (`get_train_lfb`, the reference's cfg.GET_TRAIN_LFB), else TEST_LISTS.  Keeps
+        `image_paths` and the video-name tables for the frame store's `fetch`."""
+        c = cfg.CHARADES
+        lists = c.TRAIN_LISTS if (split == "train" or get_train_lfb) else c.TEST_LISTS
+        image_paths, image_labels, video_idx_to_name, video_name_to_idx = dataset_helper.load_image_lists(
+            [os.path.join(c.FRAME_LIST_DIR, name) for name in lists])
+        index = cls(image_paths, image_labels, split, lfb_infer_only)
+        index.image_paths, index.video_idx_to_name, index.video_name_to_idx = image_paths, video_idx_to_name, video_name_to_idx
+        return index
 
     def get_db_size(self):
         if self.lfb_infer_only:

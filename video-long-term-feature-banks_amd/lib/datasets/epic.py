@@ -4,11 +4,13 @@ Index arithmetic only, as datasets.charades.  Random draws take an explicit `rng
 module (the reference draws the clip centre with `random.randint` and the train annotation with `np.random.choice`)."""
 import collections
 import csv
+import os
 import random
 
 import numpy as np
 
 from core.config import config as cfg
+from datasets import dataset_helper
 
 CENTER_CROP_INDEX = 1
 TRAIN_PERSON_INDICES = range(1, 26)
@@ -91,6 +93,22 @@ class EpicIndex(object):
         part = cfg.TRAIN if self.is_train else cfg.TEST
         self.sample_rate, self.video_length, self.batch_size = part.SAMPLE_RATE, part.VIDEO_LENGTH, part.BATCH_SIZE
         self.seq_len = self.video_length * self.sample_rate
+
+    @classmethod
+    def from_cfg(cls, split, lfb_infer_only, shift=None, get_train_lfb=False):
+        """the index of the files EpicDataset._get_data reads: the frame lists of EPIC.FRAME_LIST_DIR (TRAIN_LISTS for
+        split 'train' or a train-bank pass, `get_train_lfb`, else TEST_LISTS) and, outside a bank pass, the annotations
+        EPIC.ANNOTATION_DIR / EPIC.ANNOTATIONS of the split's participants.  Keeps `image_paths` (by video name, in the
+        lists' order) and the video-name tables for the frame store's `fetch`."""
+        e = cfg.EPIC
+        is_train = split == "train"
+        lists = e.TRAIN_LISTS if (is_train or get_train_lfb) else e.TEST_LISTS
+        image_paths, _, video_idx_to_name, video_name_to_idx = dataset_helper.load_image_lists(
+            [os.path.join(e.FRAME_LIST_DIR, name) for name in lists], return_dict=True)
+        annotations = None if lfb_infer_only else load_annotations(os.path.join(e.ANNOTATION_DIR, e.ANNOTATIONS), is_train)
+        index = cls(image_paths, annotations, split, lfb_infer_only, shift)
+        index.image_paths, index.video_idx_to_name, index.video_name_to_idx = image_paths, video_idx_to_name, video_name_to_idx
+        return index
 
     def get_db_size(self):
         return len(self.annotations)

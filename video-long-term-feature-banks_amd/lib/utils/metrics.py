@@ -20,6 +20,8 @@ from __future__ import absolute_import, division, print_function, unicode_litera
 import collections
 import datetime
 import logging
+import os
+import pickle
 
 import numpy as np
 import torch
@@ -90,8 +92,12 @@ class MetricsCalculator(object):
     test-mode net (no label blob) is metered against (Engine.attach_meter)."""
 
     def __init__(self, engine, split, video_idx_to_name=None, total_num_boxes=None, test_labels=None, ava_groundtruth=None,
-                 excluded_keys=None, class_whitelist=None, categories=None, ava_table_rows=None):
-        """ava_groundtruth: read_csv's (boxes, labels, scores) -- with it an AVA config is scored (frame-mAP);
+                 excluded_keys=None, class_whitelist=None, categories=None, ava_table_rows=None, keep_predictions=False):
+        """keep_predictions: on a single-label test split the meter also keeps the first TEST.DATASET_SIZE prediction rows
+        and labels on the device (vlfb_topk_hits_keep) and finalize_metrics writes them as epic_predictions_<name>.pkl
+        (metrics.py:222-226), the input of vlfb.epic_eval.evaluate_actions.  With more than one rank this raises
+        NotImplementedError: the reference's gather order of a multi-GPU test is not reproduced.
+        ava_groundtruth: read_csv's (boxes, labels, scores) -- with it an AVA config is scored (frame-mAP);
         excluded_keys / class_whitelist / categories: read_exclusions' and read_labelmap's results; ava_table_rows: rows of
         the score table (default: every row ceil(TEST.DATASET_SIZE / TEST.BATCH_SIZE) iterations issue, padding included)"""
         self.model = self.engine = engine
@@ -111,6 +117,10 @@ class MetricsCalculator(object):
         self.excluded_keys = set(excluded_keys) if excluded_keys else set()
         self.class_whitelist = set(class_whitelist) if class_whitelist else None
         self.categories = categories
+        self.keep_predictions = bool(keep_predictions) and not cfg.MODEL.MULTI_LABEL and split != 'train'
+        if self.keep_predictions and dist.world_size() > 1:
+            raise NotImplementedError("keep_predictions: the kept prediction table is single-process only (world size %d)"
+                                      % dist.world_size())
         from vlfb.engine import LossStep
         heads = [st for st in engine.steps if isinstance(st, LossStep) and st.prob is not None]
         if cfg.DATASET == 'ava' and ava_groundtruth is not None and heads and split != 'train':
@@ -128,7 +138,8 @@ class MetricsCalculator(object):
                     self.meter = DeviceMeter("map", cols, n_items=max(total // self.num_test_clips, 1), total_rows=total,
                                              device=engine.device)
             else:
-                self.meter = DeviceMeter("topk", cols, ks=(1, 5), device=engine.device)
+                keep = int(cfg.TEST.DATASET_SIZE) if self.keep_predictions else None
+                self.meter = DeviceMeter("topk", cols, ks=(1, 5), device=engine.device, keep_rows=keep)
             if self.meter is not None:
                 engine.attach_meter(self.meter, labels=test_labels)
         self.reset()
@@ -214,8 +225,10 @@ class MetricsCalculator(object):
             )).format(curr_iter + 1, total_iters, timer.diff, cur_batch_size, self.aggr_batch_size)
             print(test_str + tail)
 
-    def finalize_metrics(self, is_train=False, name='latest'):
-        """the final figures: mAP of the merged table (Charades), or the aggregated top-1 / top-5 error"""
+    def finalize_metrics(self, is_train=False, name='latest', out_dir=None):
+        """the final figures: mAP of the merged table (Charades), or the aggregated top-1 / top-5 error.  A calculator
+        built with keep_predictions also writes epic_predictions_<name>.pkl = (float32 [n][cols], int32 [n]), pickle
+        protocol 2, into `out_dir` (default: the current directory, as the reference does)."""
         if cfg.DATASET == 'ava' and self.ava_groundtruth is None:
             raise NotImplementedError(
                 "AVA frame-mAP: the reference does not ship its evaluator (utils/ava_eval_helper.py imports "
@@ -266,6 +279,14 @@ class MetricsCalculator(object):
                 self.full_map = self.results["mean_ap"]
         else:
             self._read_topk()
+            if not is_train and self.meter.keep_rows:
+                table, labels = self.meter.kept()
+                # stack_predictions (metrics.py:147-163): every row of the split was tested, at most a batch of padding cut
+                assert table.shape[0] == self.meter.keep_rows, "%d of %d predictions were issued" % (table.shape[0], self.meter.keep_rows)
+                self.predictions = (table.cpu().numpy(), labels.cpu().numpy())
+                self.predictions_file = os.path.join(out_dir if out_dir is not None else os.getcwd(), 'epic_predictions_%s.pkl' % name)
+                with open(self.predictions_file, 'wb') as f:
+                    pickle.dump(self.predictions, f, protocol=2)
 
     def get_computed_metrics(self):
         json_stats = {}

@@ -18,6 +18,13 @@ def get_crop_size(split):
     return cfg.TEST.CROP_SIZE if split in ("test", "val") else cfg.TRAIN.CROP_SIZE
 
 
+def get_total_test_iters(test_model):
+    """iterations of one pass over a test split, the last batch padded (reference: misc.py:279-281).  `test_model`: an
+    object whose `input_db` has get_db_size(), or such an index itself (datasets.*.…Index)"""
+    db = getattr(test_model, "input_db", None) or test_model
+    return -(-int(db.get_db_size()) // int(cfg.TEST.BATCH_SIZE))
+
+
 def unscope_name(blob_name):
     blob_name = str(blob_name)
     return blob_name[blob_name.rfind(_SCOPE_SEP) + 1:]

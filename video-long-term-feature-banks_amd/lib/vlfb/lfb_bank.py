@@ -140,9 +140,11 @@ class DeviceBank(object):
     dim = property(lambda self: self.desc.dim)
 
     def _rows_of(self, videos):
-        v = np.asarray(videos).astype(np.int64).reshape(-1)
         if self.video_row is None:
-            return v
+            return np.asarray(videos).astype(np.int64).reshape(-1)
+        if any(isinstance(x, str) for x in videos):          # names (EPIC verb banks); a negative number is a padding row
+            return np.array([self.video_row.get(x, -1) if isinstance(x, str) else -1 for x in videos], dtype=np.int64)
+        v = np.asarray(videos).astype(np.int64).reshape(-1)
         return np.array([self.video_row.get(int(x), -1) if x >= 0 else -1 for x in v], dtype=np.int64)
 
     def _dev_i32(self, arr):
@@ -181,6 +183,18 @@ class DeviceBank(object):
         steps[:n] = (fk[:n, 1] + 1) // sample_freq - 1
         return self.append_keys(vids, steps + self.step_base)
 
+    def epic_frame_keys(self, rows, frame_keys, sample_freq):
+        """`frame_keys` for an EPIC verb bank: (video, frame) pairs with frame % sample_freq == 0, step = frame //
+        sample_freq (epic.py get_annotations_for_lfb_frames; the step rule of `from_epic`) -> keys of `rows` rows, those
+        beyond len(frame_keys) marked as padding"""
+        n = min(int(rows), len(frame_keys))
+        vids = [k[0] for k in frame_keys[:n]] + [-1] * (int(rows) - n)
+        frames = np.array([int(k[1]) for k in frame_keys[:n]], dtype=np.int64)
+        assert np.all(frames % sample_freq == 0), "frame keys must be LFB frames"
+        steps = np.zeros(int(rows), dtype=np.int64)
+        steps[:n] = frames // sample_freq
+        return self.append_keys(vids, steps + self.step_base)
+
     def append_enqueue(self, feats, keys_dev, rows):
         """`append` for a caller that owns every buffer (a bank-construction pass): feats a contiguous (>= rows, dim) DEVICE
         tensor (fp32 / bf16), keys_dev the `append_keys` / `frame_keys` it uploaded in stream order.  One launch on the
@@ -209,6 +223,21 @@ class DeviceBank(object):
 
     def counts(self):
         return self.count.view(self.n_videos, self.n_steps).cpu().numpy()
+
+    def count_nonfinite(self):
+        """(bad_rows, occupied_rows): the occupied rows that hold a NaN or +-Inf element and the occupied rows examined,
+        counted on the device (vlfb_lfb_count_nonfinite); 16 bytes come back.  Synchronises."""
+        out = torch.zeros(2, device=self.device, dtype=torch.int64)
+        hip.call("vlfb_lfb_count_nonfinite", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(out))
+        bad, occupied = out.cpu().tolist()
+        return int(bad), int(occupied)
+
+    def check_finite(self):
+        """a finished bank holds no NaN / Inf row: on the 16-bit paths an activation above the format's range turns into one
+        silently, and an inference pass has no loss to notice it"""
+        bad, occupied = self.count_nonfinite()
+        if bad:
+            raise hip.VlfbError("lfb bank: %d of %d occupied rows hold a NaN or Inf element" % (bad, occupied))
 
     # ---- sampling --------------------------------------------------------------------------------
     def _out(self, out, shape, dtype):
@@ -388,8 +417,9 @@ class DeviceBank(object):
         bank.check_no_drops()
         return bank
 
-    def to_reference(self, frame_level=False, sample_freq=None, chunk_rows=65536):
-        """the reference's dictionaries, fp32: {video: {sec: [feat, ...]}} or, frame_level, {video: {frame: feat}}.  Reads the
+    def to_reference(self, frame_level=False, sample_freq=None, chunk_rows=65536, epic=False):
+        """the reference's dictionaries, fp32: {video: {sec: [feat, ...]}} or, frame_level, {video: {frame: feat}} with the
+        frame of step s = sample_freq * (s + 1) - 1 (Charades) or, `epic`, sample_freq * s (EPIC verb).  Reads the
         bank through `packed_chunks`: the device memory it takes is one staging chunk plus the offsets, whatever the bank's size."""
         out = {(self.video_ids[vi] if self.video_ids is not None else vi): {} for vi in range(self.n_videos)}
         names = list(out)
@@ -400,7 +430,7 @@ class DeviceBank(object):
                 steps = out[names[k[r, 0]]]
                 s = int(k[r, 1])
                 if frame_level:
-                    steps.setdefault(int(sample_freq * (s + 1) - 1), f[r].copy())
+                    steps.setdefault(int(sample_freq * s if epic else sample_freq * (s + 1) - 1), f[r].copy())
                 else:
                     steps.setdefault(s + self.step_base, []).append(f[r].copy())
         return out

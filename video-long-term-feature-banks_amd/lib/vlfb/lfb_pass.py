@@ -1,4 +1,4 @@
-"""The bank-construction pass for AVA and the bank's files (reference: tools/lfb_loader.py:115-236).
+"""The bank-construction passes and the bank's files (reference: tools/lfb_loader.py:49-236).
 
 The reference runs the baseline model in lfb_infer_only test mode over every keyframe, fetches `box_pooled` and `metadata`
 to the host after every iteration, builds {video: {sec: [feat, ...]}} there and pickles it.  Here the features never visit
@@ -6,6 +6,10 @@ the host: `box_pooled` is appended to a vlfb.lfb_bank.DeviceBank by a kernel, wi
 metadata and uploaded in stream order, and the files are written from the bank's packed rows.
 
     bank = get_lfb(cfg.LFB.MODEL_PARAMS_FILE, is_train=True, store=make_store)     # a DeviceBank, built, loaded or both
+
+Charades and EPIC-Kitchens verbs (frame-level banks, construct_frame_level_lfb, :49-76): one `pool5` row per clip, under the
+clip's (video, centre frame); `build_frame_bank` is the same loop on `pool5`.  EPIC nouns have no inference pass: that
+bank comes from detector files and is only loaded.
 """
 import collections
 import os
@@ -73,6 +77,83 @@ def build_ava_bank(engine, loader, index, store, bank, rng=None):
     return bank
 
 
+def frame_minibatch_source(index, store, bank_video=None):
+    """generator of what FrameLoader.start takes for one pass over a Charades / EPIC index outside train: the clips
+    0 .. db_size in order, in batches, the last one padded with its first clip (get_minibatch_info); clips as (store, video,
+    frame_numbers); meta = dict(iteration=, videos=, centers=, padded=[bool per clip]).  bank_video: the index's video ->
+    the key a sampled bank knows it by (default: the same)."""
+    n = index.batch_size // cfg.NUM_GPUS
+    size = index.get_db_size()
+    for it, lo in enumerate(range(0, size, n)):
+        batch = list(range(lo, min(lo + n, size)))
+        infos = index.get_minibatch_info(batch)
+        videos = [c.video if bank_video is None else bank_video(c.video) for c in infos]
+        meta = dict(iteration=it, videos=videos, centers=[c.center for c in infos],
+                    padded=[k >= len(batch) for k in range(len(infos))])
+        yield [(store, c.video, c.seq) for c in infos], [c.labels for c in infos], meta, None, [c.shift for c in infos]
+
+
+def frame_pass_keys(bank, kind, meta, rows):
+    """the (rows, 2) int32 append keys of one iteration of a frame-level pass: row r of `pool5` is clip r of the minibatch
+    and carries its (video, centre frame); the clips that only pad a short last batch get video -1 (skipped by the append).
+    The reference stops at len(all_metadata) as well (lfb_loader.py:61)."""
+    padded = list(meta["padded"])
+    real = padded.index(True) if True in padded else len(padded)
+    assert not any(not p for p in padded[real:]), "padding clips come last"
+    keys = list(zip(meta["videos"], meta["centers"]))[:real]
+    if kind == "charades":
+        return bank.frame_keys(rows, keys, cfg.CHARADES.FPS // cfg.CHARADES.LFB_CLIPS_PER_SECOND)
+    return bank.epic_frame_keys(rows, keys, cfg.EPIC.FPS // cfg.EPIC.VERB_LFB_CLIPS_PER_SECOND)
+
+
+def build_frame_bank(engine, loader, index, store, bank, kind):
+    """the loop of tools/lfb_loader.py:200-223 for Charades (`kind` "charades") and EPIC verbs ("epic_verb"): `engine` an
+    lfb_infer_only basic-head engine planned in test mode, `loader` its FrameLoader, `index` an lfb_infer_only CharadesIndex
+    / EpicIndex, `store` the FrameStore (on the loader's stream) whose `fetch` decodes, `bank` a DeviceBank of capacity 1
+    whose rows are the index's video indices (Charades) or carry the video names as `video_ids` (EPIC).  Per batch: next /
+    deliver / forward / append_enqueue(pool5); nothing in the loop waits for the device.  At the end one synchronisation,
+    check_no_drops, check_finite (a pass has no loss whose NaN guard would notice an overflowed activation) and the store's
+    check_decoded."""
+    assert kind in ("charades", "epic_verb"), kind
+    metas = collections.deque()                       # the source runs in the loader's thread, one minibatch ahead
+
+    def source():
+        for args in frame_minibatch_source(index, store):
+            metas.append(args[2])
+            yield args
+
+    feats, _ = engine.blob_tensor("pool5")
+    rows = loader.N
+    assert feats.numel() == rows * bank.dim, "pool5 holds %d elements, %d clips x %d planned" % (feats.numel(), rows, bank.dim)
+    loader.start(source())
+    try:
+        while True:
+            try:
+                mb = loader.next()
+            except StopIteration:
+                break
+            loader.deliver(mb)
+            engine.forward()
+            # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
+            pin = torch.from_numpy(frame_pass_keys(bank, kind, metas.popleft(), rows)).pin_memory()
+            bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
+    finally:
+        loader.stop()
+    torch.cuda.current_stream().synchronize()
+    bank.check_no_drops()
+    bank.check_finite()
+    store.check_decoded()                             # frames the store decoded from JPEG bytes: none was damaged
+    return bank
+
+
+def frame_sample_freq():
+    """frames between two bank clips of the configured frame-level dataset (EPIC: of the verb bank, or of the noun bank)"""
+    if cfg.DATASET == "charades":
+        return cfg.CHARADES.FPS // cfg.CHARADES.LFB_CLIPS_PER_SECOND
+    per_second = cfg.EPIC.NOUN_LFB_FRAMES_PER_SECOND if cfg.EPIC.CLASS_TYPE == "noun" else cfg.EPIC.VERB_LFB_CLIPS_PER_SECOND
+    return cfg.EPIC.FPS // per_second
+
+
 def lfb_paths(directory, is_train):
     """(the reference's pickle, the native file next to it)"""
     stem = os.path.join(directory, "train_lfb" if is_train else "val_lfb")
@@ -81,8 +162,9 @@ def lfb_paths(directory, is_train):
 
 def load_lfb(is_train, dtype="bf16", device="cuda:0", capacity=None):
     """train_lfb.pkl / val_lfb.pkl under LFB.LOAD_LFB_PATH -> DeviceBank.  The native .npz next to the pickle wins when
-    present (packed rows in the bank's own type, nothing converted); the pickle is the reference's {video: {sec: [feat,
-    ...]}}, written by Python 2 or 3."""
+    present (packed rows in the bank's own type, nothing converted); the pickle is the reference's, written by Python 2 or
+    3: {video: {sec: [feat, ...]}} (AVA), {video index: {frame: feat}} (Charades), {video name: {frame: feat}} (EPIC verbs)
+    or {video index: {frame: (n, dim) detector features or []}} (EPIC nouns)."""
     pkl, npz = lfb_paths(cfg.LFB.LOAD_LFB_PATH, is_train)
     if os.path.exists(npz):
         return DeviceBank.load(npz, device=device)
@@ -92,15 +174,28 @@ def load_lfb(is_train, dtype="bf16", device="cuda:0", capacity=None):
         except TypeError:
             f.seek(0)
             lfb = pickle.load(f)
+    if cfg.DATASET == "charades":
+        return DeviceBank.from_reference(lfb, dtype=dtype, device=device, frame_level=True, sample_freq=frame_sample_freq())
+    if cfg.DATASET == "epic":
+        noun = cfg.EPIC.CLASS_TYPE == "noun"
+        return DeviceBank.from_epic(lfb, noun=noun, sample_freq=frame_sample_freq(), capacity=capacity if noun else None,
+                                    dtype=dtype, device=device)
     return DeviceBank.from_reference(lfb, capacity=capacity, dtype=dtype, device=device)
 
 
 def write_lfb(bank, is_train, native=True):
     """train_lfb.pkl / val_lfb.pkl under CHECKPOINT.DIR in the reference's format (fp32 features; protocol 2, the highest
-    the reference's Python 2 reads) and, next to it, the native .npz `load_lfb` prefers"""
+    the reference's Python 2 reads) and, next to it, the native .npz `load_lfb` prefers.  Charades and EPIC-verb banks are
+    written as {video: {frame: feat}} with the reference's frame numbers."""
     pkl, npz = lfb_paths(cfg.CHECKPOINT.DIR, is_train)
+    if cfg.DATASET in ("charades", "epic"):
+        if cfg.DATASET == "epic" and cfg.EPIC.CLASS_TYPE == "noun":
+            raise NotImplementedError("write_lfb: an EPIC noun bank comes from detector files, no pass infers one to write")
+        lfb = bank.to_reference(frame_level=True, sample_freq=frame_sample_freq(), epic=cfg.DATASET == "epic")
+    else:
+        lfb = bank.to_reference()
     with open(pkl, "wb") as f:
-        pickle.dump(bank.to_reference(), f, 2)
+        pickle.dump(lfb, f, 2)
     if native:
         bank.save(npz)
     return pkl
@@ -111,7 +206,10 @@ def get_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capac
     """lfb_loader.get_lfb: the bank loaded from LFB.LOAD_LFB_PATH when LFB.LOAD_LFB, else inferred with the baseline
     parameters `params_file` over every keyframe of the train (is_train) or test LFB box lists, and written when
     LFB.WRITE_LFB.  `store(device, stream)` builds the datasets.frame_store.FrameStore (with its `fetch`) on the loader's
-    stream; `max_src_hw` bounds its frames.  `capacity`: slots per second, default the most boxes any keyframe has."""
+    stream; `max_src_hw` bounds its frames.  `capacity`: slots per second, default the most boxes any keyframe has.
+    Charades and EPIC verbs: the frame-level pass (get_frame_lfb); EPIC nouns can only be loaded."""
+    if cfg.DATASET in ("charades", "epic"):
+        return get_frame_lfb(params_file, is_train, store, dtype, bank_dtype, capacity, device, n_slots, max_src_hw)
     from datasets.clip_loader import MinibatchLoader
     from models.model_builder_video import ModelBuilder
     from utils import checkpoints
@@ -138,6 +236,64 @@ def get_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capac
     bank = DeviceBank(index.num_videos, last - ava.AVA_VALID_FRAMES[0] + 1, capacity or most, cfg.LFB.LFB_DIM, bank_dtype,
                       device, step_base=ava.AVA_VALID_FRAMES[0])
     build_ava_bank(engine, loader, index, frames, bank, rng)
+    if cfg.LFB.WRITE_LFB:
+        write_lfb(bank, is_train)
+    return bank
+
+
+def get_frame_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capacity=None, device="cuda:0", n_slots=2,
+                  max_src_hw=(256, 340)):
+    """get_lfb for cfg.DATASET 'charades' / 'epic': loaded when LFB.LOAD_LFB, else inferred with the lfb_infer_only
+    basic-head engine (planned without `proposals`) over every bank clip of the train (is_train) or test frame lists,
+    checked for the reference's completeness conditions (construct_lfb, lfb_loader.py:140-152) and written when
+    LFB.WRITE_LFB.  Bank geometry: capacity 1, n_steps from the longest video; rows = video indices (Charades) or the videos
+    in the order of the frame lists with their names as `video_ids` (EPIC verbs)."""
+    from datasets import charades, epic
+    from datasets.clip_loader import FrameLoader
+    from models.model_builder_video import ModelBuilder
+    from utils import checkpoints
+    from vlfb.engine import Engine
+    if cfg.LFB.LOAD_LFB:
+        return load_lfb(is_train, bank_dtype, device, capacity)
+    if cfg.DATASET == "epic" and cfg.EPIC.CLASS_TYPE == "noun":
+        raise NotImplementedError("get_lfb: the EPIC noun bank holds detector features (the reference has no inference pass "
+                                  "for it either); set LFB.LOAD_LFB and LFB.LOAD_LFB_PATH to the detector-built files")
+    assert params_file, "LFB.MODEL_PARAMS_FILE is not specified."
+    split = cfg.TEST.DATA_TYPE or "test"
+    sample_freq = frame_sample_freq()
+    if cfg.DATASET == "charades":
+        kind = "charades"
+        index = charades.CharadesIndex.from_cfg(split, True, get_train_lfb=is_train)
+        n_videos, video_ids = index.num_videos, None
+        n_steps = max(max(index.num_frames) // sample_freq, 1)
+    else:
+        kind = "epic_verb"
+        index = epic.EpicIndex.from_cfg(split, True, shift=1, get_train_lfb=is_train)
+        video_ids = list(index.image_paths)
+        n_videos = len(video_ids)
+        n_steps = max([a[2] for a in index.annotations] + [0]) // sample_freq + 1
+    suffix = "_infer_%s" % ("train" if is_train else "test")
+    model = ModelBuilder(train=False, split=split, name="lfb_infer")
+    model.build_model(suffix=suffix, lfb_infer_only=True, shift=1)
+    engine = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED)
+    n = cfg.TEST.BATCH_SIZE // cfg.NUM_GPUS
+    shapes = {"data" + suffix: (n, 3, cfg.TEST.VIDEO_LENGTH, cfg.TEST.CROP_SIZE, cfg.TEST.CROP_SIZE),
+              "labels" + suffix: (n, cfg.MODEL.NUM_CLASSES) if cfg.MODEL.MULTI_LABEL else (n,)}
+    engine.plan(collections.OrderedDict((name, shapes[name]) for name in model.input_blob_names))
+    engine.init_params()
+    checkpoints.load_model_from_params_file_for_test(model, params_file)
+    loader = FrameLoader(engine, suffix, 0, n_slots=n_slots, max_src_hw=max_src_hw, device=device)
+    frames = store(loader.device, loader.stream)
+    bank = DeviceBank(n_videos, n_steps, 1, cfg.LFB.LFB_DIM, bank_dtype, device, video_ids=video_ids)
+    build_frame_bank(engine, loader, index, frames, bank, kind)
+    occupied = bank.counts() > 0
+    with_clips = int(occupied.any(axis=1).sum())
+    if cfg.DATASET == "charades":
+        want = cfg.TRAIN.DATASET_SIZE if is_train else cfg.TEST.DATASET_SIZE
+        assert with_clips == want, "the bank holds %d videos, the split has %d" % (with_clips, want)
+    assert with_clips == n_videos, "%d of %d videos have no bank clip" % (n_videos - with_clips, n_videos)
+    assert int(occupied.sum()) == index.get_db_size(), \
+        "%d bank cells are occupied, the pass walked %d clips" % (int(occupied.sum()), index.get_db_size())
     if cfg.LFB.WRITE_LFB:
         write_lfb(bank, is_train)
     return bank

@@ -4,7 +4,9 @@ The reference's meter (lib/utils/metrics.py) fetches `pred` and `labels` from ev
 this engine is a replayed call list or a captured graph that never synchronises, so the meter is a set of kernels with
 constant arguments that sit inside the step and add into device state; `read()` is the one call that synchronises.
 
-  kind "topk"  single-label heads (EPIC verbs / nouns): hits for every k of `ks` and the number of rows counted
+  kind "topk"  single-label heads (EPIC verbs / nouns): hits for every k of `ks` and the number of rows counted; with
+               keep_rows=N also the first N prediction rows and their labels (vlfb_topk_hits_keep: what the reference's
+               finalize_metrics writes as epic_predictions_<name>.pkl), `kept()`
   kind "map"   multi-label heads (Charades): a score table [n_items][cols] into which every prediction row is merged by
                max at (stream position % n_items) -- clip c of video i arrives at position i + c * n_items, which is
                aggregate_predictions_from_clips (metrics.py:165-186) done while the clips arrive -- and from which
@@ -48,8 +50,12 @@ class DeviceMeter(object):
     """One device buffer: hit counters, cursor, mismatch counter, score table, label table, per-class outputs, sort
     workspace.  `update` issues kernels on the current stream and returns nothing; `read` synchronises."""
 
-    def __init__(self, kind, cols, ks=(1, 5), n_items=None, total_rows=0, device=None):
+    def __init__(self, kind, cols, ks=(1, 5), n_items=None, total_rows=0, device=None, keep_rows=None):
         assert kind in ("topk", "map", "ava"), kind
+        assert keep_rows is None or kind == "topk", "keep_rows belongs to a 'topk' meter (the other kinds keep their table)"
+        self.keep_rows = int(keep_rows) if keep_rows is not None else 0
+        if keep_rows is not None and self.keep_rows < 1:
+            raise hip.VlfbError("DeviceMeter: keep_rows = %r must be at least 1" % (keep_rows,))
         self.kind, self.cols = kind, int(cols)
         self.ks = tuple(int(k) for k in ks)
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
@@ -63,6 +69,7 @@ class DeviceMeter(object):
         self._ks = hip.ks_array(self.ks)
         # layout (bytes): hits int64[5] | cursor int64 | mismatches int32 (+pad) | ap f64[cols] | auc f64[cols] |
         #                 n_pos int32[cols] | table f32[n][cols] | labels u8[n][cols] | sort workspace
+        #                 ("topk" with keep_rows = N: table f32[N][cols] | labels int32[N])
         n, c = self.n_items, self.cols
         off = {"hits": 0, "cursor": 40, "mismatch": 48}
         at = 64
@@ -72,6 +79,8 @@ class DeviceMeter(object):
             sizes += [("table", 4 * n * c), ("labels", n * c), ("ws", self.ws_bytes)]
         elif kind == "ava":                          # (tp, ap, n_gt and the sort workspace belong to one ava_frame_ap call)
             sizes += [("table", 4 * n * c), ("labels", n * c)]
+        elif self.keep_rows:
+            sizes += [("table", 4 * self.keep_rows * c), ("labels", 4 * self.keep_rows)]
         for name, nbytes in sizes:
             off[name] = at
             at = _align(at + nbytes)
@@ -90,6 +99,9 @@ class DeviceMeter(object):
         elif kind == "ava":
             self.table = view("table", 4 * n * c, torch.float32).view(n, c)
             self.labels = view("labels", n * c, torch.uint8).view(n, c)
+        elif self.keep_rows:
+            self.table = view("table", 4 * self.keep_rows * c, torch.float32).view(self.keep_rows, c)
+            self.labels = view("labels", 4 * self.keep_rows, torch.int32)
         self.reset()
 
     def reset(self):
@@ -101,7 +113,10 @@ class DeviceMeter(object):
 
     def update_ptr(self, scores_ptr, dtype, labels_ptr, rows):
         """scores [rows][cols] of `dtype` and int32 labels ([rows] class indices / [rows][cols] multi-hot) by address"""
-        if self.kind == "topk":
+        if self.kind == "topk" and self.keep_rows:
+            hip.call("vlfb_topk_hits_keep", scores_ptr, dtype, labels_ptr, rows, self.cols, self._ks[0], self._ks[1],
+                     hip.ptr(self.hits), hip.ptr(self.table), hip.ptr(self.labels), self.keep_rows, hip.ptr(self.cursor))
+        elif self.kind == "topk":
             hip.call("vlfb_topk_hits", scores_ptr, dtype, labels_ptr, rows, self.cols, self._ks[0], self._ks[1],
                      hip.ptr(self.hits))
         else:
@@ -120,6 +135,14 @@ class DeviceMeter(object):
         head = self.head.cpu().numpy()
         nk = len(self.ks) if self.kind == "topk" else 0
         return [int(v) for v in head[:nk]], int(head[nk]), int(head[5]), int(head[6] & 0xffffffff)
+
+    def kept(self):
+        """a "topk" meter with keep_rows: (table[:n], labels[:n]) device views of the rows kept so far, n = min(cursor,
+        keep_rows); one sync"""
+        if not self.keep_rows:
+            raise hip.VlfbError("DeviceMeter.kept: this meter was built without keep_rows")
+        n = min(self.counters()[2], self.keep_rows)
+        return self.table[:n], self.labels[:n]
 
     def filled(self, cursor):
         n = min(cursor, self.total_rows) if self.total_rows > 0 else cursor
