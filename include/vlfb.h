@@ -429,6 +429,39 @@ int vlfb_bn_bwd(const void* dy, const void* x, const float* gamma, const float* 
                 int64_t workspace_bytes, int dtype, int64_t rows, int64_t C, float grad_scale,
                 vlfb_stream_t stream);
 
+/* Precise BN (lib/utils/bn_helper.py): before a checkpoint or an evaluation the running statistics of every SpatialBN
+ * layer are replaced by the average of the batch statistics of a number of training batches.  All three entry points
+ * read one layer table in DEVICE memory, `layers` records of vlfb_bn_layer; a layer's channels occupy
+ * [offset, offset + C) of the packed fp32 accumulators.  One workgroup per layer (grid-stride over the layers), one
+ * thread per channel (block-stride over C): the offsets are not known on the host, and nothing but `layers` is.
+ *   accumulate: per (layer, channel), fp32, unfused (bn_helper.py:170-182):
+ *                 r = 1 / save_inv_std; var = r * r - eps; m2 = var + save_mean * save_mean;
+ *                 sum_mean += save_mean; sum_mean2 += m2              (divisions are correctly rounded)
+ *   finalize:   in place, mean = sum_mean / float(normalize); m2 = sum_mean2 / float(normalize); var = m2 - mean * mean;
+ *               sum_mean <- mean, sum_mean2 <- var (bn_helper.py:187-198).  *bad (int32, device memory) is SET to the
+ *               number of channels whose var is not > 0 (NaN included): zeroed on the stream, then integer atomic adds.
+ *               The running statistics are not touched: the reference asserts var > 0 before it writes anything.
+ *   update:     running_mean <- mean[offset ...], running_var <- var[offset ...] of every layer (bn_helper.py:200-221:
+ *               the "riv" blob is the running VARIANCE).  May be repeated.
+ * VLFB_ERR_ARG before anything is launched: layers <= 0, normalize <= 0, a NULL table / accumulator / bad.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct vlfb_bn_layer {
+  const float* save_mean;      /* [C] batch mean of the last training forward */
+  const float* save_inv_std;   /* [C] 1 / sqrt(batch var + eps) */
+  float* running_mean;         /* [C] */
+  float* running_var;          /* [C] */
+  int64_t offset;              /* first element of the layer in the packed accumulators */
+  int32_t C;
+  int32_t reserved;
+} vlfb_bn_layer;
+#define VLFB_BN_LAYER_BYTES 48
+int vlfb_bn_precise_accumulate(const vlfb_bn_layer* table, int layers, float eps, float* sum_mean, float* sum_mean2,
+                               vlfb_stream_t stream);
+int vlfb_bn_precise_finalize(const vlfb_bn_layer* table, int layers, int normalize, float* sum_mean, float* sum_mean2,
+                             int32_t* bad, vlfb_stream_t stream);
+int vlfb_bn_precise_update(const vlfb_bn_layer* table, int layers, const float* mean, const float* var,
+                           vlfb_stream_t stream);
+
 /* LayerNorm over each row, no learnable scale/bias, eps inside sqrt (lfb_helper.py:160-166,
  * 252-256; Caffe2 LayerNorm axis=1).  rstd[r] = 1/sqrt(var+eps) saved for backward. */
 int vlfb_layernorm_fwd(const void* x, void* y, float* rstd, int dtype, int64_t rows, int64_t cols,

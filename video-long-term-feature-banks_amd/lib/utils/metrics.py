@@ -147,6 +147,7 @@ class MetricsCalculator(object):
     def reset(self):
         logger.info('Resetting {} metrics...'.format(self.split))
         self.aggr_loss = 0.0
+        self._loss_count = 0                         # (the average restarts with the sum)
         self.aggr_batch_size = 0
         self._last = (0, 0, 0)                       # hits@1, hits@5, rows at the previous read
         self.avg_loss = self.avg_err = self.avg_err5 = float('nan')
@@ -183,11 +184,14 @@ class MetricsCalculator(object):
         self.aggr_batch_size = rows
         return err(p1, prow), err(p5, prow), self.avg_err, self.avg_err5
 
-    def calculate_and_log_all_metrics_train(self, curr_iter, timer, suffix=''):
+    def calculate_and_log_all_metrics_train(self, curr_iter, timer, suffix='', losses=None):
+        """losses: the values of a read of the device loss ring the caller already made at this iteration (the training
+        driver's NaN guard drains the ring); default: read it here"""
         if (curr_iter + 1) % cfg.LOG_PERIOD != 0:
             return
         self.lr = float(self.engine.lr)
-        losses = self.engine.recent_losses()
+        if losses is None:
+            losses = self.engine.recent_losses()
         cur_loss = losses[-1] if losses else float('nan')
         if losses:
             self.aggr_loss += float(np.sum(losses))
@@ -330,3 +334,27 @@ class MetricsCalculator(object):
             self.best_top1 = self.avg_err
             self.best_top5 = self.avg_err5
             print('\n* Best model: top1: {:7.3f} top5: {:7.3f}\n'.format(self.best_top1, self.best_top5))
+
+
+def get_json_stats_dict(train_meter, test_meter, curr_iter):
+    """Define stats that will be logged (reference metrics.py:566-593: the same keys in the same order)."""
+    import utils.misc as misc
+    json_stats = {
+        "eval_period": cfg.TRAIN.EVAL_PERIOD,
+        "batchSize": cfg.TRAIN.BATCH_SIZE,
+        "dataset": cfg.DATASET,
+        "num_classes": cfg.MODEL.NUM_CLASSES,
+        "momentum": cfg.SOLVER.MOMENTUM,
+        "weightDecay": cfg.SOLVER.WEIGHT_DECAY,
+        "nGPU": cfg.NUM_GPUS,
+        "LR": cfg.SOLVER.BASE_LR,
+        "bn_momentum": cfg.MODEL.BN_MOMENTUM,
+        "current_learning_rate": train_meter.lr,
+    }
+    json_stats.update(train_meter.get_computed_metrics())
+    if test_meter is not None:
+        json_stats.update(test_meter.get_computed_metrics())
+    json_stats['used_gpu_memory'] = misc.get_gpu_stats()
+    json_stats['currentIter'] = curr_iter + 1
+    json_stats['epoch'] = curr_iter / (cfg.TRAIN.DATASET_SIZE / cfg.TRAIN.BATCH_SIZE)
+    return json_stats

@@ -25,6 +25,30 @@ def get_total_test_iters(test_model):
     return -(-int(db.get_db_size()) // int(cfg.TEST.BATCH_SIZE))
 
 
+def generate_random_seed(node_id=0):
+    """reference misc.py:275-276"""
+    import numpy as np
+    np.random.seed(cfg.RNG_SEED)
+
+
+def get_gpu_stats():
+    """the `used_gpu_memory` field of the JSON stats line (reference misc.py:150-164 parses `nvidia-smi -q`): the bytes the
+    process holds on the current device, as the reference's string of MiB; 'n/a' without a device"""
+    import torch
+    if not torch.cuda.is_available():
+        return "n/a"
+    return "%d MiB" % (torch.cuda.memory_reserved() >> 20)
+
+
+def log_json_stats(stats):
+    """reference misc.py:82-84"""
+    import json
+    import logging
+    line = '\njson_stats: {:s}\n'.format(json.dumps(stats, sort_keys=False))
+    logging.getLogger(__name__).info(line)
+    return line
+
+
 def unscope_name(blob_name):
     blob_name = str(blob_name)
     return blob_name[blob_name.rfind(_SCOPE_SEP) + 1:]

@@ -147,6 +147,30 @@ LFB_PACK_TILE = 1024                                # vlfb.h VLFB_LFB_PACK_TILE:
 LFB_PACK_MAX_CELLS = LFB_PACK_TILE * LFB_PACK_TILE  # vlfb.h VLFB_LFB_PACK_MAX_CELLS: what its two levels cover
 
 
+class BnLayer(C.Structure):
+    """vlfb.h vlfb_bn_layer: one SpatialBN layer of the precise-BN table (device addresses)"""
+    _fields_ = [(n, C.c_uint64) for n in ("save_mean", "save_inv_std", "running_mean", "running_var")] + \
+               [("offset", C.c_int64), ("C", C.c_int32), ("reserved", C.c_int32)]
+
+
+BN_LAYER_BYTES = 48                                 # vlfb.h VLFB_BN_LAYER_BYTES
+assert C.sizeof(BnLayer) == BN_LAYER_BYTES
+
+
+def bn_layer_table(layers, device):
+    """device copy of a precise-BN layer table: layers = [(save_mean, save_inv_std, running_mean, running_var, C)] of fp32
+    tensors / addresses; returns (uint8 tensor holding the records, packed elements).  Offsets are consecutive."""
+    import numpy as np
+    recs = (BnLayer * len(layers))()
+    off = 0
+    for r, (sm, siv, rm, rv, ch) in zip(recs, layers):
+        r.save_mean, r.save_inv_std, r.running_mean, r.running_var = ptr(sm), ptr(siv), ptr(rm), ptr(rv)
+        r.offset, r.C = off, int(ch)
+        off += int(ch)
+    host = torch.from_numpy(np.frombuffer(bytes(recs), dtype=np.uint8).copy())
+    return host.to(device), off
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _SIGS = {
@@ -196,6 +220,9 @@ _SIGS = {
     "vlfb_bn_workspace_bytes": (_I64, [C.c_int, _I64, _I64]),
     "vlfb_bn_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, _I64, _I64, C.c_float, C.c_float, C.c_int, _P]),
     "vlfb_bn_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, _I64, _I64, C.c_float, _P]),
+    "vlfb_bn_precise_accumulate": (C.c_int, [_P, C.c_int, C.c_float, _P, _P, _P]),
+    "vlfb_bn_precise_finalize": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "vlfb_bn_precise_update": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "vlfb_layernorm_fwd": (C.c_int, [_P, _P, _P, C.c_int, _I64, _I64, C.c_float, _P]),
     "vlfb_layernorm_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int, _I64, _I64, _P]),
     "vlfb_dropout_fwd": (C.c_int, [_P, _P, _P, C.c_int, _I64, _I64, _I64, C.c_float, C.c_uint64, _P]),

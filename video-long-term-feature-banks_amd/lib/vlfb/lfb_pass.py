@@ -93,6 +93,40 @@ def frame_minibatch_source(index, store, bank_video=None):
         yield [(store, c.video, c.seq) for c in infos], [c.labels for c in infos], meta, None, [c.shift for c in infos]
 
 
+def train_index_walk(size, n, rng):
+    """the endless index walk of a training loader (dataloader.py:180-221): a permutation of 0 .. size drawn with
+    rng.shuffle at the start, and again whenever the next batch of n would reach or run past the end -- so the tail of a
+    permutation is never used, as in the reference"""
+    assert size > 0 and n > 0, "an empty training index"
+
+    def shuffled():
+        perm = list(range(size))
+        rng.shuffle(perm)
+        return perm
+    perm, current = shuffled(), 0
+    while True:
+        if current + n >= size:
+            perm, current = shuffled(), 0
+        yield perm[current:current + n]
+        current += n
+
+
+def frame_train_source(index, store, rng, bank_video=None, aug_rng=None):
+    """endless generator of what FrameLoader.start takes for TRAINING on a Charades / EPIC index: the batches of
+    train_index_walk, get_minibatch_info(batch, rng) (which draws the clip's centre, for EPIC the annotation, from the same
+    `rng`, an object with random.Random's methods), the tuple layout of frame_minibatch_source.  aug_rng: the numpy-style
+    generator of the crop / flip / colour draws (default np.random, as in the reference)."""
+    assert index.split == "train", "frame_train_source is the training source (other passes: frame_minibatch_source)"
+    n = index.batch_size // cfg.NUM_GPUS
+    aug_rng = np.random if aug_rng is None else aug_rng
+    for it, batch in enumerate(train_index_walk(index.get_db_size(), n, rng)):
+        infos = index.get_minibatch_info(list(batch), rng)
+        videos = [c.video if bank_video is None else bank_video(c.video) for c in infos]
+        meta = dict(iteration=it, videos=videos, centers=[c.center for c in infos],
+                    padded=[k >= len(batch) for k in range(len(infos))])
+        yield [(store, c.video, c.seq) for c in infos], [c.labels for c in infos], meta, aug_rng, 1
+
+
 def frame_pass_keys(bank, kind, meta, rows):
     """the (rows, 2) int32 append keys of one iteration of a frame-level pass: row r of `pool5` is clip r of the minibatch
     and carries its (video, centre frame); the clips that only pad a short last batch get video -1 (skipped by the append).

@@ -1,0 +1,297 @@
+"""The training driver (reference: tools/train_net.py:49-212): `train` chains the loaders, the engine step, the NaN guard,
+checkpoints, precise BN, the periodic evaluation on shared parameters and the JSON stats line.
+
+    train(make_store)                                    # make_store(device, stream) -> FrameStore with its fetch
+
+One deviation in the build order: the reference builds the test model first ("so that we don't overwrite init") because
+both nets initialise the same workspace blobs.  Here the TRAIN engine owns the parameters and the test engine is built
+second with share_params_with= it; there is one initialisation, the train engine's.
+"""
+import collections
+import logging
+import os
+import random
+
+import numpy as np
+
+from core.config import config as cfg
+from utils import misc
+from vlfb import lfb_pass
+from vlfb.test_pass import Timer
+
+logger = logging.getLogger(__name__)
+
+Wrapper = collections.namedtuple("Wrapper", "model engine index loader store timer meter suffix bank_video")
+
+
+def _bank_kind():
+    if cfg.DATASET == 'charades':
+        return "charades"
+    return "epic_noun" if cfg.EPIC.CLASS_TYPE == 'noun' else "epic_verb"
+
+
+def _ava_rows(index, n):
+    """RoI rows of a plan: clips per GPU x the most boxes any keyframe of the index has"""
+    most = max(len(index.boxes_and_labels[v][s]) for v, s, _ in index.keyframe_indices)
+    return n * most
+
+
+def create_wrapper(is_train, make_store, lfb, owner=None, dtype="mix", device="cuda:0", n_slots=2, max_src_hw=(256, 340),
+                   ava_groundtruth=None, excluded_keys=(), class_whitelist=None, categories=None, suffix=None, force_fw_only=False):
+    """train_net.py:49-90: the model, its planned engine, the dataset index, the loader (AvaIndex + MinibatchLoader for AVA,
+    CharadesIndex / EpicIndex + FrameLoader otherwise; not started), the frame store on the loader's stream, a timer and the
+    MetricsCalculator.  `owner`: the engine whose parameters this one aliases (the train engine, for the test wrapper and
+    the precise-BN aux engine).  -> Wrapper"""
+    from datasets import ava, charades, epic
+    from datasets.clip_loader import FrameLoader, MinibatchLoader
+    from models.model_builder_video import ModelBuilder
+    from vlfb.engine import Engine
+    import utils.metrics as metrics
+    if is_train:
+        suffix, split, part = suffix or '_train', cfg.TRAIN.DATA_TYPE, cfg.TRAIN
+    else:
+        suffix, split, part = suffix or '_test', cfg.TEST.DATA_TYPE, cfg.TEST
+    model = ModelBuilder(train=is_train, split=split, name=split, force_fw_only=force_fw_only)
+    model.build_model(suffix=suffix, lfb=lfb)
+    engine = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED, share_params_with=owner)
+    n = part.BATCH_SIZE // cfg.NUM_GPUS
+    bank_video = None
+    if cfg.DATASET == 'ava':
+        index = ava.AvaIndex.from_cfg(split, False)
+        rows = _ava_rows(index, n)
+        k = cfg.LFB.WINDOW_SIZE * cfg.AVA.LFB_MAX_NUM_FEAT_PER_STEP
+        shapes = {"data" + suffix: (n, 3, part.VIDEO_LENGTH, part.CROP_SIZE, part.CROP_SIZE),
+                  "labels" + suffix: (rows, cfg.MODEL.NUM_CLASSES), "proposals" + suffix: (rows, 5),
+                  "lfb" + suffix: (rows, k, cfg.LFB.LFB_DIM)}
+    else:
+        if cfg.DATASET == 'charades':
+            index = charades.CharadesIndex.from_cfg(split, False)
+        else:
+            index = epic.EpicIndex.from_cfg(split, False, shift=None if is_train else cfg.TEST.CROP_SHIFT)
+            if _bank_kind() == "epic_noun":              # the noun bank is keyed by video index, the verb bank by name
+                bank_video = index.video_name_to_idx.__getitem__
+        shapes = {"data" + suffix: (n, 3, part.VIDEO_LENGTH, part.CROP_SIZE, part.CROP_SIZE),
+                  "labels" + suffix: (n, cfg.MODEL.NUM_CLASSES) if cfg.MODEL.MULTI_LABEL else (n,),
+                  "lfb" + suffix: (n, cfg.LFB.WINDOW_SIZE, cfg.LFB.LFB_DIM)}
+    engine.plan(collections.OrderedDict((blob, shapes[blob]) for blob in model.input_blob_names))
+    uses_bank = ("lfb" + suffix) in model.input_blob_names
+    assert not uses_bank or lfb is not None, "the model reads a feature bank (LFB.ENABLED): no bank was given"
+    aug = 1 if (is_train and split == "train") else 0
+    if cfg.DATASET == 'ava':
+        loader = MinibatchLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=lfb if uses_bank else None,
+                                 device=device)
+    else:
+        loader = FrameLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=lfb if uses_bank else None,
+                             bank_kind=_bank_kind() if uses_bank else None, device=device)
+    store = make_store(loader.device, loader.stream)
+    meter = None
+    if not force_fw_only:
+        scored = cfg.DATASET == 'ava' and not is_train
+        meter = metrics.MetricsCalculator(
+            engine, split, video_idx_to_name=index.video_idx_to_name,
+            ava_groundtruth=ava_groundtruth if scored else None, excluded_keys=excluded_keys if scored else None,
+            class_whitelist=class_whitelist if scored else None, categories=categories if scored else None,
+            ava_table_rows=(misc.get_total_test_iters(index) * shapes["labels" + suffix][0]) if scored else None)
+    return Wrapper(model, engine, index, loader, store, Timer(), meter, suffix, bank_video)
+
+
+def train_source(w, rng, aug_rng):
+    """what the wrapper's loader is started with for training: ava.minibatch_source (shuffled per pass with `aug_rng`, a
+    numpy generator) or lfb_pass.frame_train_source (`rng`: random.Random's methods)"""
+    from datasets import ava
+    if cfg.DATASET == 'ava':
+        return ava.minibatch_source(w.index, w.store, aug_rng, bank=w.loader.bank)
+    return lfb_pass.frame_train_source(w.index, w.store, rng, w.bank_video, aug_rng=aug_rng)
+
+
+def eval_pass(test, name='latest', curr_iter=None, rng=None):
+    """the in-training evaluation (train_net.py:184-196) on the test wrapper, whose engine aliases the parameters being
+    trained: reset, one pass over the test split, finalize_metrics / compute_and_log_best / log_final_metrics.  Charades /
+    EPIC: the loop of test_one_crop; nothing is loaded and no predictions are kept.  AVA: the single-crop pass -- the
+    test AvaIndex (built under AVA.FULL_EVAL = FULL_EVAL_DURING_TRAINING, DETECTION_SCORE_THRESH = _TRAIN), centre crop,
+    add_ava_batch(metadata, original_boxes) per iteration.  -> iterations run"""
+    import torch
+    from datasets import ava
+    from vlfb import dist
+    if dist.world_size() > 1:
+        raise NotImplementedError("eval_pass: the in-training evaluation is single-process (world size %d)" % dist.world_size())
+    meter, loader, engine = test.meter, test.loader, test.engine
+    meter.reset()
+    logger.info("=> Testing model")
+    total = misc.get_total_test_iters(test.index)
+    if cfg.DATASET == 'ava':
+        # (its own generator: the training loader's thread draws from np.random while this pass runs)
+        source = ava.minibatch_source(test.index, test.store, np.random.RandomState(cfg.RNG_SEED) if rng is None else rng,
+                                      bank=loader.bank)
+    else:
+        source = lfb_pass.frame_minibatch_source(test.index, test.store, test.bank_video)
+    loader.start(source)
+    test_iter = -1
+    try:
+        for test_iter in range(total):
+            test.timer.tic()
+            mb = loader.next()
+            loader.deliver(mb)
+            engine.forward()
+            test.timer.toc()
+            if cfg.DATASET == 'ava' and meter.meter is not None:
+                meter.add_ava_batch(mb.metadata[:, :2], mb.original_boxes)
+            meter.calculate_and_log_all_metrics_test(test_iter, test.timer, total, test.suffix)
+    finally:
+        loader.stop()
+    torch.cuda.current_stream().synchronize()
+    test.store.check_decoded()
+    if cfg.DATASET == 'ava' and meter.ava_groundtruth is None:
+        meter.full_map = 0.0                             # (no annotation files were given: nothing to score against)
+    else:
+        meter.finalize_metrics(name=name)
+    meter.compute_and_log_best()
+    meter.log_final_metrics(curr_iter if curr_iter is not None else test_iter, None if curr_iter is not None else total)
+    return test_iter + 1
+
+
+def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groundtruth=None, excluded_keys=(),
+          class_whitelist=None, categories=None, n_slots=2, max_src_hw=(256, 340), train_lfb=None, test_lfb=None, init_params=None,
+          on_eval=None, eval_dtype=None):
+    """Train a model (train_net.py:93-212).  make_store(device, stream) -> the FrameStore (with its fetch) of a loader.
+    train_lfb / test_lfb: banks already built (default with LFB.ENABLED: lfb_pass.get_lfb for test, then train);
+    init_params(train_engine): sets the initial parameters (default: the recorded fillers, Engine.init_params);
+    on_eval(curr_iter, train_wrapper, test_wrapper, json_stats): called after every evaluation;
+    eval_dtype: the dtype of the forward-only engines -- bank inference, the test engine, test_net (default: `dtype`, and
+    "bf16", the default of the test passes, where that is "mix": `mix` is a training path).
+    -> dict(last_checkpoint=, json_stats=[...], train=, test=, bn_aux=, eval_iters=[...], final=)"""
+    import torch
+    from utils import checkpoints
+    import utils.metrics as metrics
+    from vlfb import test_pass
+
+    # Generate seed.
+    misc.generate_random_seed()
+    rng = random.Random(cfg.RNG_SEED)
+    checkpoint_dir = checkpoints.create_and_get_checkpoint_directory()
+    logger.info('Checkpoint directory created: {}'.format(checkpoint_dir))
+
+    # Setting training-time-specific configurations (put back when the loop ends; test_net sets its own).
+    before = (cfg.AVA.get("FULL_EVAL"), cfg.AVA.get("DETECTION_SCORE_THRESH"), cfg.CHARADES.get("NUM_TEST_CLIPS"))
+    cfg.AVA.FULL_EVAL = cfg.AVA.FULL_EVAL_DURING_TRAINING
+    cfg.AVA.DETECTION_SCORE_THRESH = cfg.AVA.DETECTION_SCORE_THRESH_TRAIN
+    cfg.CHARADES.NUM_TEST_CLIPS = cfg.CHARADES.NUM_TEST_CLIPS_DURING_TRAINING
+
+    if eval_dtype is None:
+        eval_dtype = "bf16" if dtype == "mix" else dtype
+    if cfg.LFB.ENABLED:
+        kw = dict(dtype=eval_dtype, bank_dtype=bank_dtype, device=device, n_slots=n_slots, max_src_hw=max_src_hw)
+        if test_lfb is None:
+            test_lfb = lfb_pass.get_lfb(cfg.LFB.MODEL_PARAMS_FILE, False, make_store, **kw)
+        if train_lfb is None:
+            train_lfb = lfb_pass.get_lfb(cfg.LFB.MODEL_PARAMS_FILE, True, make_store, **kw)
+
+    common = dict(device=device, n_slots=n_slots, max_src_hw=max_src_hw)
+    # The train engine owns the parameters; the test engine aliases them (module docstring).
+    tr = create_wrapper(True, make_store, train_lfb, dtype=dtype, **common)
+    if init_params is None:
+        tr.engine.init_params()
+    else:
+        init_params(tr.engine)
+    te = create_wrapper(False, make_store, test_lfb, owner=tr.engine, ava_groundtruth=ava_groundtruth, excluded_keys=excluded_keys,
+                        class_whitelist=class_whitelist, categories=categories, dtype=eval_dtype, **common)
+    total_test_iters = misc.get_total_test_iters(te.index)
+    logger.info('Test iters: {}'.format(total_test_iters))
+
+    bn_aux, aux = None, []
+    out = dict(last_checkpoint=None, json_stats=[], train=tr, test=te, bn_aux=None, eval_iters=[], final=None)
+    try:
+        if cfg.TRAIN.COMPUTE_PRECISE_BN:
+            from vlfb.precise_bn import PreciseBN
+
+            def make_loader(engine, suffix):
+                from datasets.clip_loader import FrameLoader, MinibatchLoader
+                aug = 1 if cfg.TRAIN.DATA_TYPE == "train" else 0
+                if cfg.DATASET == 'ava':
+                    loader = MinibatchLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=tr.loader.bank, device=device)
+                else:
+                    loader = FrameLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=tr.loader.bank,
+                                         bank_kind=tr.loader.bank_kind, device=device)
+                w = tr._replace(loader=loader, store=make_store(loader.device, loader.stream))
+                aux.append(w)
+                # its own walk over the training split, as the reference's bn_aux model has its own data loader
+                loader.start(train_source(w, random.Random(cfg.RNG_SEED + 1), np.random.RandomState(cfg.RNG_SEED + 1)))
+                return loader
+            bn_aux = out["bn_aux"] = PreciseBN(tr.engine, make_loader)
+
+        # Load checkpoint or pre-trained weight.
+        start_model_iter = 0
+        if cfg.CHECKPOINT.RESUME or cfg.TRAIN.PARAMS_FILE:
+            start_model_iter = checkpoints.load_model_from_params_file(tr.model)
+        out["start_model_iter"] = start_model_iter
+
+        logger.info("------------- Training model... -------------")
+        tr.meter.reset()
+        last_checkpoint = checkpoints.get_checkpoint_resume_file()
+        unlogged = []                                        # losses the guard read since the meter's last line
+        tr.loader.start(train_source(tr, rng, np.random))
+        for curr_iter in range(start_model_iter, cfg.SOLVER.MAX_ITER):
+            tr.model.UpdateWorkspaceLr(curr_iter)            # lr_policy.get_lr_at_iter, and the momentum correction
+            tr.timer.tic()
+            tr.loader.deliver(tr.loader.next())
+            tr.engine.train_step(float(tr.model.current_lr))
+            tr.timer.toc()
+
+            # the NaN guard reads the device loss ring, one synchronisation: at the iterations the meter reads it anyway
+            # (LOG_PERIOD), at least once per ring, and before anything is saved or evaluated
+            saves = (curr_iter + 1) % cfg.CHECKPOINT.CHECKPOINT_PERIOD == 0 or curr_iter + 1 == cfg.SOLVER.MAX_ITER
+            evals = (curr_iter + 1) % cfg.TRAIN.EVAL_PERIOD == 0
+            logs = (curr_iter + 1) % cfg.LOG_PERIOD == 0
+            if logs or saves or evals or (curr_iter + 1 - start_model_iter) % 64 == 0:
+                unlogged.extend(misc.check_nan_losses(tr.model))
+
+            # Checkpoint.
+            if saves:
+                if bn_aux is not None:
+                    bn_aux.compute_and_update_bn_stats(curr_iter)
+                last_checkpoint = os.path.join(checkpoint_dir, 'c2_model_iter{}.pkl'.format(curr_iter + 1))
+                checkpoints.save_model_params(model=tr.model, params_file=last_checkpoint, model_iter=curr_iter)
+
+            if logs:
+                tr.meter.calculate_and_log_all_metrics_train(curr_iter, tr.timer, suffix='_train', losses=list(unlogged))
+                del unlogged[:]
+
+            # Evaluation.
+            if evals:
+                if bn_aux is not None:
+                    bn_aux.compute_and_update_bn_stats(curr_iter)
+                ran = eval_pass(te, curr_iter=curr_iter)
+                out["eval_iters"].append(ran)
+                # Finalize and reset train_meter after test.
+                if cfg.DATASET == 'ava':
+                    tr.meter.full_map = 0.0              # (no mAP while training; the train meter holds no annotation files)
+                else:
+                    tr.meter.finalize_metrics(is_train=True)
+                json_stats = metrics.get_json_stats_dict(tr.meter, te.meter, curr_iter)
+                misc.log_json_stats(json_stats)
+                out["json_stats"].append(json_stats)
+                if on_eval is not None:
+                    on_eval(curr_iter, tr, te, json_stats)
+                tr.meter.reset()
+        out["last_checkpoint"] = last_checkpoint
+    finally:
+        tr.loader.stop()
+        te.loader.stop()
+        for w in aux:
+            w.loader.stop()
+        for part, key, value in ((cfg.AVA, "FULL_EVAL", before[0]), (cfg.AVA, "DETECTION_SCORE_THRESH", before[1]),
+                                 (cfg.CHARADES, "NUM_TEST_CLIPS", before[2])):
+            if value is None:
+                part.pop(key, None)
+            else:
+                part[key] = value
+    torch.cuda.current_stream().synchronize()
+
+    if cfg.TRAIN.TEST_AFTER_TRAIN:
+        kw = dict(dtype=eval_dtype, device=device)
+        if cfg.DATASET != 'ava':
+            kw.update(n_slots=n_slots, max_src_hw=max_src_hw)
+        cfg.TEST.PARAMS_FILE = out["last_checkpoint"]
+        out["final"] = test_pass.test_net(out["last_checkpoint"], make_store, lfb=test_lfb, ava_groundtruth=ava_groundtruth,
+                                          excluded_keys=excluded_keys, class_whitelist=class_whitelist, **kw)
+    return out
