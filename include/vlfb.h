@@ -341,6 +341,21 @@ int vlfb_maxpool_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax
  * kt*kh*kw / (st*sh*sw) times less mask traffic. */
 int vlfb_maxpool_relu_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax, const void* y, void* dx,
                           vlfb_stream_t stream);
+/* A two-plane FPROP launch (math VLFB_MATH_F16X3, out_dtype VLFB_F16) and the max-pool behind it in ONE launch, for a conv
+ * output that nothing but the pool reads (pool2 behind res2's last conv: resnet_video.py:229-236): the epilogue forms the two
+ * planes every output row would have stored, takes the window maximum on hi + lo with a strict > in tap order -- what
+ * vlfb_maxpool_fwd does on the stored planes -- and stores only the pooled planes and the arg-max bytes; the un-pooled
+ * tensor is never written.  `d` and `pool` are the unchanged descriptors of the two separate launches; a->O / a->O_lo are the
+ * POOLED planes (y and y + numel of vlfb_maxpool_fwd), every other operand is what vlfb_conv_run_args takes (no Mask, P,
+ * O_planes, dbias); argmax as vlfb_maxpool_fwd, NULL in inference.  Bit-identical to vlfb_conv_run_args followed by
+ * vlfb_maxpool_fwd.  Implemented: the temporal pool (2x1x1, stride 2x1x1, no padding) behind a plain-row conv that plans
+ * on the 128 x 128 two-plane kernel with prefetched residual rows ("nt_pair f16x3 128x128 pre"); any frame size, odd frame
+ * counts (the last frame has no window and is not computed), ragged column tiles.  Any other pair of descriptors is
+ * VLFB_ERR_UNSUPPORTED before anything is launched; vlfb_conv_maxpool_fusable answers the same question (1 / 0) at plan
+ * time. */
+int vlfb_conv_maxpool_fusable(const vlfb_conv_desc* d, const vlfb_pool_desc* pool);
+int vlfb_conv_run_maxpool(const vlfb_conv_desc* d, const vlfb_pool_desc* pool, const vlfb_conv_args* a, void* argmax,
+                          vlfb_stream_t stream);
 /* average over the window (pad 0 only, as every AveragePool in the reference) */
 int vlfb_avgpool_fwd(const vlfb_pool_desc* d, const void* x, void* y, vlfb_stream_t stream);
 int vlfb_avgpool_bwd(const vlfb_pool_desc* d, const void* dy, void* dx, const void* add,

@@ -10,8 +10,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def family(name):
-    # the two-plane fp16 instances (vlfb_gemm_pair.hip): PAIR is the 13th template argument of gemm_nt_kernel (W2I follows it),
-    # the 7th of gemm_nt8_kernel
+    # the two-plane fp16 instances (vlfb_gemm_pair.hip): PAIR is the 13th template argument of gemm_nt_kernel (W2I and POOL2 --
+    # pool2 in the epilogue, a two-plane instance as well -- follow it), the 7th of gemm_nt8_kernel
     m = re.search(r"gemm_(nt8?)_kernel<([^>]*)>\(", name)
     if m:
         targs = [a.strip() for a in m.group(2).split(",")]

@@ -931,6 +931,65 @@ extern "C" int vlfb_conv_run_args(const vlfb_conv_desc* d, const vlfb_conv_args*
                        a->O_planes, a->dbias, stream, a->R_lo, a->O_lo);
 }
 
+// conv + max-pool in one launch (vlfb_conv_run_maxpool): the plan of `d` and, when the pair cannot be fused, the reason.
+// Implemented: the temporal pool (2x1x1, stride 2x1x1, no padding) behind a two-plane plain-row conv that plans on the
+// 128 x 128 kernel with prefetched residual rows (gemm_nt_kernel POOL2).
+static int conv_maxpool_plan(const vlfb_conv_desc* d, const vlfb_pool_desc* pd, Plan* pl, const char** why) {
+  *why = nullptr;
+  VLFB_REQUIRE(d && pd, "conv_maxpool: both descriptors are required");
+  const int rc = cached_plan(d, pl);
+  if (rc != VLFB_OK) return rc;
+  const GP& g = pl->gp;
+  if (d->mode != VLFB_CONV_FPROP || d->dtype != VLFB_F16 || d->math != VLFB_MATH_F16X3 || d->out_dtype != VLFB_F16)
+    *why = "the conv is not a two-plane fp16 FPROP with a two-plane output";
+  else if (pd->dtype != VLFB_F16PAIR || pd->N != d->N || pd->Ti != d->Tr || pd->Hi != d->Hr || pd->Wi != d->Wr || pd->C != d->Cn)
+    *why = "the pool does not read the conv's two-plane output";
+  else if (pd->kt != 2 || pd->kh != 1 || pd->kw != 1 || pd->st != 2 || pd->sh != 1 || pd->sw != 1 || pd->pt || pd->ph || pd->pw ||
+           pd->To < 1 || pd->To != d->Tr / 2 || pd->Ho != d->Hr || pd->Wo != d->Wr)
+    *why = "only the 2x1x1 pool with stride 2x1x1 and no padding is fused";
+  else if (pl->family != Family::nt_pair || !pl->ident || pl->bm != 128 || pl->bn != 128 || !pl->pre || !g.vec_epi)
+    *why = "the conv does not plan on the 128 x 128 two-plane plain-row kernel with prefetched residual rows";
+  else if (d->batch > 1 || d->o_planes || d->bias_mode == VLFB_BIAS_ROW || g.ldo != d->Cn)
+    *why = "batched launches, plane copies, row biases and strided output rows are not fused";
+  return VLFB_OK;
+}
+
+extern "C" int vlfb_conv_maxpool_fusable(const vlfb_conv_desc* d, const vlfb_pool_desc* pool) {
+  Plan pl;
+  const char* why;
+  if (conv_maxpool_plan(d, pool, &pl, &why) != VLFB_OK) return 0;
+  return why == nullptr;
+}
+
+extern "C" int vlfb_conv_run_maxpool(const vlfb_conv_desc* d, const vlfb_pool_desc* pool, const vlfb_conv_args* a,
+                                     void* argmax, vlfb_stream_t stream) {
+  VLFB_REQUIRE(a, "conv_run_maxpool: arguments are required");
+  Plan pl;
+  const char* why;
+  int rc = conv_maxpool_plan(d, pool, &pl, &why);
+  if (rc != VLFB_OK) return rc;
+  if (why) return set_error(VLFB_ERR_UNSUPPORTED, "conv_run_maxpool: %s", why);
+  VLFB_REQUIRE(a->A && a->B && a->O && a->O_lo, "conv_run_maxpool: A, B and both pooled planes (O, O_lo) are required");
+  VLFB_REQUIRE(!a->Mask && !a->O_planes && !a->dbias && !a->P, "conv_run_maxpool: no mask, plane copy, dbias or P operand");
+  VLFB_REQUIRE(!a->R_lo || a->R, "conv: R_lo without R");
+  VLFB_REQUIRE(d->bias_mode == VLFB_BIAS_NONE || a->bias != nullptr, "conv: bias_mode set but bias is NULL");
+  GP& g = pl.gp;
+  g.A = (const char*)a->A; g.B = (const char*)a->B; g.O = (char*)a->O; g.O2 = (char*)a->O_lo;
+  g.bias = a->bias; g.R = (const char*)a->R; g.R2 = (const char*)a->R_lo;
+  g.AM = (unsigned char*)argmax;
+  g.p2_hw = d->Hr * d->Wr;
+  g.p2_chunks = (g.p2_hw + 63) / 64;
+  g.p2_to = pool->To;
+  g.tiles_m = d->N * pool->To * g.p2_chunks;       // one row tile per (frame pair, chunk of 64 positions)
+  static const int nt_epi = env_int("VLFB_NT_EPI", 1);
+  g.nt_epi = nt_epi >= 1;                          // (a two-plane launch: the rule of conv_run_impl)
+  // the fp32 tile is staged through LDS in ONE pass (the epilogue visits rows r and r + 64 back to back): 64 KiB, what a
+  // launch with two k-tiles or more has anyway
+  const size_t tile = (size_t)128 * 128 * 4;
+  g.epi = 1;
+  return launch_nt_pair_pool2(g, dim3((unsigned)(g.tiles_m * g.tiles_n), 1, 1), pl.lds < tile ? tile : pl.lds, (hipStream_t)stream);
+}
+
 extern "C" int vlfb_conv_run_planes(const vlfb_conv_desc* d, const void* A, const void* B, const void* P,
                                     void* O, const float* bias, const float* rowscale, const void* R,
                                     const void* Mask, void* workspace, int64_t workspace_bytes, void* O_planes,

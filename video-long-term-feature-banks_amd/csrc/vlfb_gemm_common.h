@@ -62,6 +62,14 @@ struct GP {
   // it streams through the L2 instead of evicting the operand panels the other workgroups of the XCD are re-reading
   // (set per launch in conv_run_impl, VLFB_NT_EPI; measured per launch and in the step)
   int nt_epi;
+  // two-plane NT launch with the temporal max-pool of its output (2x1x1, stride 2x1x1) in the epilogue (gemm_nt_kernel
+  // POOL2, vlfb_conv_run_maxpool): row tile = (frame pair, chunk of 64 positions); rows 0-63 are the chunk's positions of
+  // frame 2 tau, rows 64-127 the same positions of frame 2 tau + 1.  O / O2 are the POOLED planes, AM the arg-max bytes (may
+  // be null); the un-pooled rows are not stored.
+  int p2_hw;          // positions of one frame (Hr * Wr)
+  int p2_chunks;      // chunks of 64 positions per frame
+  int p2_to;          // frame pairs per clip (pooled T)
+  unsigned char* AM;
 };
 
 // vlfb_gemm8.hip: 256-row phase-pipelined NT kernel.  bm = 256 | 196 (two wave rows of 98), bn = 256 | 128; mode 0 = plain rows, 1 = gathered
@@ -109,6 +117,8 @@ int launch_nt_planes(const GP& gp, int npl, int bn, int kind, dim3 grid, size_t 
 // vlfb_gemm_pair.hip: VLFB_MATH_F16X3 -- both operands as two fp16 planes (GP::a_ps / b_ps apart), plain rows or scalar tap cursor
 int launch_nt_pair(const GP& gp, int bn, bool ident, bool pre, bool out_f32, dim3 grid, size_t lds, hipStream_t s);
 int launch_nt8_pair(const GP& gp, int bm, int bn, int mode, bool out_f32, hipStream_t s);
+// ... the 128 x 128 plain-row form with the temporal max-pool of its two-plane output in the epilogue (GP::p2_*)
+int launch_nt_pair_pool2(const GP& gp, dim3 grid, size_t lds, hipStream_t s);
 
 namespace {
 

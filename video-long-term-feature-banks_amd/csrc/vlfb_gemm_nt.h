@@ -10,7 +10,7 @@ namespace {
 // NT kernel: O[m][n] = sum_k X[m][k] * W[n][k]   (X gathered: FPROP / DGRAD / identity)
 // =============================================================================================
 template <typename T, typename OutT, int BM, int BN, bool IDENT, bool DGRAD, bool PACKW, int RB, bool PRE, int NW,
-          int ST = 2, bool UT = false, bool PAIR = false, bool W2I = false>
+          int ST = 2, bool UT = false, bool PAIR = false, bool W2I = false, bool POOL2 = false>
 __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
   // W2I (16-bit unit-stride DGRAD with TWO-TERM weights, vlfb_conv_desc.math = VLFB_MATH_F16W2; the backward of the "mix"
   // path): the weight rows are [tap][Cs / 64][term][64] (vlfb_weight_prep* VLFB_MIX_W2I), i.e. the k-tiles of the weight
@@ -33,6 +33,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
   // the address from (n, t, h, w) every tile: measured 5 VALU instructions per MFMA on the 3x3 layers
   // (SQ_INSTS_VALU 43.1 M vs SQ_INSTS_MFMA 7.2 M), more issue time than the MFMAs themselves.
   static_assert(!UT || (!IDENT && !PACKW), "UT is for gathered, unpacked operands");
+  // POOL2 (two-plane plain rows, 128 x 128 tile on 8 waves; vlfb_conv_run_maxpool): the 2x1x1 / stride 2x1x1 max-pool of the
+  // output inside the epilogue.  A row tile is a PAIR of frames: rows 0-63 are 64 consecutive positions of frame 2 tau, rows
+  // 64-127 the same positions of frame 2 tau + 1 (GP::p2_*), so the two taps of a pooled element are rows r and r + 64 of one
+  // tile -- passes gp and gp + 2 of the same lane in the LDS-staged epilogue.  Only the pooled planes and the arg-max bytes
+  // are stored.  The last frame of a clip with an odd frame count has no window and is not computed.
+  static_assert(!POOL2 || (PAIR && IDENT && sizeof(OutT) == 2 && BM == 128 && BN == 128 && NW == 8), "POOL2: the two-plane 128 x 128 plain-row kernel");
   // ST = LDS stages of the k-loop ring (tiles in flight = ST - 1, counted vmcnt on the oldest).
   // Shipped instances use ST = 2.  Measured on MI355X: ST = 5 with 64-byte tile rows (four 16 KiB
   // tiles in flight on the same 80 KiB) is 15-20 % SLOWER on the long-K res5 layers (561 vs 688
@@ -101,6 +107,21 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
     return m;
   };
 
+  // POOL2: local tile row -> row of the enumeration (= un-pooled output row) and whether it exists
+  int p2_in = 0, p2_out = 0, p2_lim = 0;
+  if constexpr (POOL2) {
+    const int pair = tile_m / p.p2_chunks, ch = tile_m - pair * p.p2_chunks;
+    const int n = pair / p.p2_to, tau = pair - n * p.p2_to;
+    p2_in = (n * p.Tr + 2 * tau) * p.p2_hw + ch * 64;       // un-pooled row of tile row 0
+    p2_out = pair * p.p2_hw + ch * 64;                      // pooled row of tile rows 0 and 64
+    p2_lim = p.p2_hw - ch * 64;                             // positions of this chunk that exist (>= 64: all of them)
+  }
+  auto p2_row = [&](int r, bool& ok) -> int {
+    ok = (r & 63) < p2_lim;
+    return p2_in + (r >> 6) * p.p2_hw + (r & 63);
+  };
+  (void)p2_out; (void)p2_row;
+
   const char* Ab = p.A + (long long)z * p.a_bs * (long long)sizeof(T);
   const char* Bb = p.B + (long long)z * p.b_bs * (long long)sizeof(T);
 
@@ -125,6 +146,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
   for (int i = 0; i < A_IT; ++i) {
     int m = m0 + r0 + RPPS * i;
     aok[i] = m < mrows;
+    if constexpr (POOL2) m = p2_row(r0 + RPPS * i, aok[i]);
     if (!IDENT) arow[i] = row_coords(aok[i] ? m : 0);
     if (UT) {
       RowC& r = arow[i];                   // (t, h, w) become the tap-(0,0,0) source coordinates
@@ -144,7 +166,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
   if (IDENT || UT) {
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
-      const int m = m0 + r0 + RPPS * i;
+      int m = m0 + r0 + RPPS * i;
+      if constexpr (POOL2) { bool rok; m = p2_row(r0 + RPPS * i, rok); }
       if (IDENT) aoff[i] = aok[i] ? (unsigned)(m * p.lda) * (unsigned)sizeof(T) + a_cb : kOOB;
       else aoff[i] = (unsigned)(upix[i] * p.lda) * (unsigned)sizeof(T) + a_cb;   // wraps for padding rows
     }
@@ -270,14 +293,17 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
   // PRE: thin-K launches are epilogue (HBM) bound, so the residual / mask rows of this lane are
   // requested BEFORE the k-loop and arrive while the MFMAs run.
   constexpr bool PREM = PRE && !PAIR;          // (PAIR launches are forward convs: no mask operand)
-  constexpr bool PRE2 = PRE && PAIR;           // (PAIR: the residual is two planes -- the low one is requested up front as well)
+  // (PAIR: the residual is two planes -- the low one is requested up front as well; not under POOL2, whose two row streams
+  // cost the registers that hold it: 134 VGPRs = one workgroup per CU instead of two)
+  constexpr bool PRE2 = PRE && PAIR && !POOL2;
   const bool nt = p.nt_epi != 0;             // epilogue rows with the non-temporal hint (GP::nt_epi)
   uint4 rpre[PRE ? NPASS : 1], mpre[PREM ? NPASS : 1], r2pre[PRE2 ? NPASS : 1];
   if (PRE) {
 #pragma unroll
     for (int gp = 0; gp < NPASS; ++gp) {
-      const int m = m0 + gp * RPP + tr;
-      const bool ok = m < mrows && ncol < p.Ncols;
+      int m = m0 + gp * RPP + tr;
+      bool ok = m < mrows && ncol < p.Ncols;
+      if constexpr (POOL2) { bool rok; m = p2_row(gp * RPP + tr, rok); ok = rok && ncol < p.Ncols; }
       const long long off = (row_pos(ok ? m : 0) * p.ldr + ncol) * (long long)sizeof(T);
       rpre[gp] = ld16_epi(nt, src_or_zero(Rb ? Rb : Ab, off, ok && Rb != nullptr));
       if constexpr (PRE2) r2pre[gp] = ld16_epi(nt, src_or_zero(R2b ? R2b : Ab, off, ok && R2b != nullptr));
@@ -435,17 +461,22 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
     };
     stage(0);
     __syncthreads();
+    // POOL2 (the tile is staged in ONE pass: vlfb_conv_run_maxpool sizes the LDS for it): the planes of tap 0 wait for tap 1
+    // in the 32 bytes of LDS their fp32 values came from -- the same lane reads them back two passes later, no barrier
 #pragma unroll
     for (int gp = 0; gp < NPASS; ++gp) {
-      if (gp == NPASS / 2 && epi == 2) {
+      if constexpr (POOL2) __builtin_amdgcn_sched_barrier(0);
+      if (!POOL2 && gp == NPASS / 2 && epi == 2) {
         __syncthreads();
         stage(1);
         __syncthreads();
       }
       const int trow = gp * RPP + tr;                                   // row inside the tile
       const int row = (epi == 2 && gp >= NPASS / 2) ? trow - BM / 2 : trow;   // row inside the staged half
-      const int m = m0 + trow;
-      if (m < mrows && ncol < p.Ncols) {
+      int m = m0 + trow;
+      bool mok = m < mrows;
+      if constexpr (POOL2) m = p2_row(trow, mok);
+      if (mok && ncol < p.Ncols) {
         const long long mpos = row_pos(m);
         float v[EPT];
 #pragma unroll
@@ -507,6 +538,45 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
         } else {
           const uint4 hv = make_uint4(Elem<OutT>::pack2(v[0], v[1]), Elem<OutT>::pack2(v[2 % EPT], v[3 % EPT]),
                                       Elem<OutT>::pack2(v[4 % EPT], v[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT], v[7 % EPT]));
+          if constexpr (POOL2) {
+            static_assert(!POOL2 || (NPASS == 4 && RPP == 32), "POOL2: passes gp and gp + 2 are rows r and r + 64");
+            // the two planes this row WOULD have stored; the window maximum is taken on their sum hi + lo with a strict >
+            // in tap order from -inf, exactly as maxpool_fwd_pair_kernel does on the stored planes (never on v itself)
+            float h[EPT];
+            unpack_elems<OutT, EPT>(hv, h);
+            const uint4 lv = make_uint4(Elem<OutT>::pack2(v[0] - h[0], v[1] - h[1]), Elem<OutT>::pack2(v[2 % EPT] - h[2 % EPT], v[3 % EPT] - h[3 % EPT]),
+                                        Elem<OutT>::pack2(v[4 % EPT] - h[4 % EPT], v[5 % EPT] - h[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT] - h[6 % EPT], v[7 % EPT] - h[7 % EPT]));
+            const int srow = row & (BM / 2 - 1);                     // the LDS row of tap 0 of this lane's window
+            uint4* const keep_h = reinterpret_cast<uint4*>(smem + ((srow * CPR + ((tc * (EPT / 4)) ^ (srow & 7))) << 4));
+            uint4* const keep_l = reinterpret_cast<uint4*>(smem + ((srow * CPR + ((tc * (EPT / 4) + 1) ^ (srow & 7))) << 4));
+            if (gp < NPASS / 2) {
+              *keep_h = hv; *keep_l = lv;
+            } else {
+              const uint4 h0 = *keep_h, l0 = *keep_l;
+              const uint32_t ah[4] = {h0.x, h0.y, h0.z, h0.w}, al[4] = {l0.x, l0.y, l0.z, l0.w};
+              const uint32_t bh[4] = {hv.x, hv.y, hv.z, hv.w}, bl[4] = {lv.x, lv.y, lv.z, lv.w};
+              uint32_t oh[4] = {0u, 0u, 0u, 0u}, ol[4] = {0u, 0u, 0u, 0u}, am[2] = {0u, 0u};
+#pragma unroll
+              for (int w = 0; w < 4; ++w) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                  const int sh = 16 * u, e = 2 * w + u;
+                  const float s0 = (u ? Elem<OutT>::hi(ah[w]) : Elem<OutT>::lo(ah[w])) + (u ? Elem<OutT>::hi(al[w]) : Elem<OutT>::lo(al[w]));
+                  const float s1 = (u ? Elem<OutT>::hi(bh[w]) : Elem<OutT>::lo(bh[w])) + (u ? Elem<OutT>::hi(bl[w]) : Elem<OutT>::lo(bl[w]));
+                  float best = -INFINITY;
+                  uint32_t sel_h = 0u, sel_l = 0u, arg = 0u;
+                  if (s0 > best) { best = s0; sel_h = (ah[w] >> sh) & 0xffffu; sel_l = (al[w] >> sh) & 0xffffu; }
+                  if (s1 > best) { sel_h = (bh[w] >> sh) & 0xffffu; sel_l = (bl[w] >> sh) & 0xffffu; arg = 1u; }
+                  oh[w] |= sel_h << sh; ol[w] |= sel_l << sh;
+                  am[e >> 2] |= arg << (8 * (e & 3));
+                }
+              }
+              const long long prow = p2_out + (trow & 63);
+              st16_epi(nt, reinterpret_cast<OutT*>(Ob) + prow * p.ldo + ncol, make_uint4(oh[0], oh[1], oh[2], oh[3]));
+              st16_epi(nt, reinterpret_cast<OutT*>(O2b) + prow * p.ldo + ncol, make_uint4(ol[0], ol[1], ol[2], ol[3]));
+              if (p.AM) st8_epi(nt, p.AM + prow * p.Ncols + ncol, make_uint2(am[0], am[1]));
+            }
+          } else {
           st16_epi(nt, o, hv);
           if (O2b) {                                 // low term: what the rounding of the stored value lost
             float h[EPT];
@@ -514,6 +584,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
             st16_epi(nt, reinterpret_cast<OutT*>(O2b) + mpos * p.ldo + ncol,
                      make_uint4(Elem<OutT>::pack2(v[0] - h[0], v[1] - h[1]), Elem<OutT>::pack2(v[2 % EPT] - h[2 % EPT], v[3 % EPT] - h[3 % EPT]),
                                 Elem<OutT>::pack2(v[4 % EPT] - h[4 % EPT], v[5 % EPT] - h[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT] - h[6 % EPT], v[7 % EPT] - h[7 % EPT])));
+          }
           }
         }
       }

@@ -52,6 +52,11 @@ int launch_nt8_pair(const GP& gp, int bm, int bn, int mode, bool out_f32, hipStr
   return out_f32 ? launch_pair8_t<float>(gp, mode, bm, bn, grid, s) : launch_pair8_t<f16_t>(gp, mode, bm, bn, grid, s);
 }
 
+// plain rows, 128 x 128, residual rows prefetched, with the temporal max-pool of the output in the epilogue (POOL2)
+int launch_nt_pair_pool2(const GP& gp, dim3 grid, size_t lds, hipStream_t s) {
+  return launch_pair_k<gemm_nt_kernel<f16_t, f16_t, 128, 128, true, false, false, 128, true, 8, 2, false, true, false, true>>(grid, 64 * 8, lds, gp, s);
+}
+
 int launch_nt_pair(const GP& gp, int bn, bool ident, bool pre, bool out_f32, dim3 grid, size_t lds, hipStream_t s) {
   if (out_f32) {
     if (bn == 64) return launch_pair_shape<float, 64, false>(gp, ident, grid, lds, s);

@@ -299,6 +299,7 @@ class ConvStep(Step):
         self.stem = (x.C == 3)
         self.eff_bias = None
         self.sparse_dgrad = False     # DGRAD as an in-place accumulate over the rows it touches (Engine._plan_sparse_shortcut_dgrads)
+        self.fused_pool = None        # the max-pool PoolStep that runs inside this conv's epilogue (Engine._plan_pool_fusion)
 
     def param_names(self):
         return (self.wname, self.cbname)
@@ -609,10 +610,17 @@ class ConvStep(Step):
             hip.conv_run(d, _at(A, g * a), W, _at(P, g * self.Cog), _at(O, g * (self.wblk if d.mode == hip.WGRAD else o)),
                          workspace=ws, **{k: _at(v, g * o) for k, v in ops.items()})
 
-    def fwd(self):
+    def fwd(self, unfused=False):
+        """unfused: the plain launch into the conv's own output, whatever was planned (Engine._rematerialise)"""
         R = self.residual.storage() if self.residual is not None else None
         A, d, half = self.x.storage(), self.d_f, self.out.root.half
         ops = dict(bias=self.bias_tensor(), R=R)
+        if self.fused_pool is not None and not unfused:
+            # conv + max-pool in one launch: only the pooled planes and the arg-max are written (Engine._plan_pool_fusion)
+            ps = self.fused_pool
+            hip.conv_run_maxpool(d, ps.desc, A, self.w_f, ps.out.storage(), ps.out.lo(), argmax=ps.argmax, bias=ops["bias"],
+                                 R=R, R_lo=self.residual.lo() if R is not None else None)
+            return
         if self.x_pair or self.o_pair:
             if self.x_planes is not None:         # the stem: the clip's two fp16 planes, made per pass
                 hip.call("vlfb_pair_split", self.x.ptr(), hip.ptr(self.x_planes), self.x_pstride)
@@ -753,6 +761,7 @@ class PoolStep(Step):
         self.inputs, self.outputs = [x], [out]
         self.k, self.s, self.p, self.is_max = kernels, strides, pads, is_max
         self.two_term_dx = False      # "mix": the fp32 pooled gradient becomes a two-term fp16 input gradient (Engine._analyse_grads)
+        self.fused_into = None        # the ConvStep whose epilogue runs this pool: fwd() issues nothing (Engine._plan_pool_fusion)
 
     def name(self):
         return ("maxpool:" if self.is_max else "avgpool:") + self.out.name
@@ -773,6 +782,8 @@ class PoolStep(Step):
             self.argmax = torch.empty(self.out.numel * nbytes, device=eng.device, dtype=torch.uint8)
 
     def fwd(self):
+        if self.fused_into is not None:
+            return                                # (the producing conv wrote the pooled planes and the arg-max)
         if self.is_max:
             hip.call("vlfb_maxpool_fwd", C.byref(self.desc), self.x.ptr(), self.out.ptr(), hip.ptr(self.argmax))
         else:
@@ -2255,7 +2266,8 @@ class Engine(object):
             self._plan_solver_buckets()
         self._plan_forward_branches()
         self._plan_half_copies()
-        self._drop_steps = [st for st in self.steps if isinstance(st, DropoutStep)]
+        self._plan_pool_fusion()
+        self._drop_steps =[st for st in self.steps if isinstance(st, DropoutStep)]
         for k, st in enumerate(self._drop_steps):
             st.seed_slot = 1 + k
         if not self.dry_run:
@@ -2787,6 +2799,7 @@ class Engine(object):
         spatial = b.shape[2:] if b.caxis == 1 else ()
         if any(int(d) != 1 for d in spatial):
             raise KeyError("blob %r is stored channels-last; use feed()/fetch()" % name)
+        self._rematerialise(b)
         t = b.tensor[:b.numel]
         return t, hip.dtype_code(t.dtype)
 
@@ -2821,6 +2834,8 @@ class Engine(object):
         b = self.env[name]
         if b.root.dead:
             raise KeyError("blob %r was fused away (its value only exists inside a kernel epilogue)" % name)
+        if not grad:
+            self._rematerialise(b.root)
         src = b.root.slot.cur if grad else b.root.tensor
         t = src.detach().float().cpu()
         if b.root.pair and not grad:              # two fp16 planes: value = hi + lo
@@ -2938,6 +2953,45 @@ class Engine(object):
         self._half_inputs = [b for b in self.all_blobs if b.root is b and b.half is not None and id(b) not in seen]
         for b in self._half_inputs:
             assert b.is_input, "blob %s has an fp16 copy that nothing writes" % b.name
+
+    # conv + max-pool in one launch (vlfb_conv_run_maxpool); read by plan().  A/B: bench.py --engine FUSE_POOL2=False
+    FUSE_POOL2 = True
+
+    def _plan_pool_fusion(self):
+        """"mix": a max-pool that is the ONLY reader of a two-plane conv output runs inside that conv's epilogue where the
+        library implements the pair (hip.conv_maxpool_fusable: pool2 behind the last conv of res2).  Execution only: the step
+        list, the blobs, their storage, descriptors and arg-max buffers stay as planned; the ConvStep launches the fused entry
+        point and the PoolStep issues nothing.  The un-pooled blob is then written by no launch of a pass: fetch() /
+        blob_tensor() re-materialise it with the plain conv launch (the conv's operands are intact behind a pass)."""
+        self._elided = {}                             # id(root) of an un-pooled blob no launch writes -> its ConvStep
+        if not (self.mix and self.FUSE_POOL2):
+            return
+        for i, st in enumerate(self.steps):
+            if not (isinstance(st, PoolStep) and st.is_max and st.x.root.pair and st.out.root.pair and st.out.root is st.out):
+                continue
+            j = self.flow.sources[i].get(id(st.x.root))
+            conv = self.steps[j] if j is not None else None
+            if not isinstance(conv, ConvStep) or conv.out.root is not st.x.root or conv.out.shape != st.x.shape:
+                continue
+            if conv.group != 1 or conv.stem or not conv.o_pair or conv.x_planes is not None or conv.fused_pool is not None:
+                continue
+            readers = self.flow.consumers_of(st.x)
+            if len(readers) != 1 or readers[0][1] is not st or st.x.root.is_input:
+                continue
+            if i in self._fwd_side or j in self._fwd_side:      # (both launches belong to the main chain)
+                continue
+            if not hip.conv_maxpool_fusable(conv.d_f, st.desc):
+                continue
+            conv.fused_pool, st.fused_into = st, conv
+            self._elided[id(st.x.root)] = conv
+
+    def _rematerialise(self, root):
+        """the values of a blob whose producing conv ran fused with the pool behind it: the plain launch of that conv into the
+        blob's storage, on the current stream (nothing else of the pass is touched: pooled planes and arg-max stay)"""
+        conv = self._elided.get(id(root))
+        if conv is not None and not self.dry_run:
+            assert hip.tracing() is None, "a blob is fetched while a step is being recorded"
+            conv.fwd(unfused=True)
 
     # independent forward branches on the second stream (Engine.forward)
     FORWARD_BRANCHES = True

@@ -204,6 +204,8 @@ _SIGS = {
     "vlfb_maxpool_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P]),
     "vlfb_maxpool_bwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P, _P, _P]),
     "vlfb_maxpool_relu_bwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P, _P]),
+    "vlfb_conv_maxpool_fusable": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(PoolDesc)]),
+    "vlfb_conv_run_maxpool": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(PoolDesc), C.POINTER(ConvArgs), _P, _P]),
     "vlfb_avgpool_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P]),
     "vlfb_avgpool_bwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P, _P]),
     "vlfb_avgpool_bwd_two_term": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P, _P]),
@@ -496,6 +498,32 @@ def conv_run(d, A, B, P, O, bias=None, rowscale=None, R=None, mask=None, workspa
         e1.record()
         prof.append((d.mode, conv_flops(d), e0, e1, conv_tag(d), conv_bytes(d, R is not None, mask is not None)) + conv_family(d))
     _check(rc, "vlfb_conv_run")
+
+
+def conv_maxpool_fusable(d, pd):
+    """whether vlfb_conv_run_maxpool implements this conv + max-pool pair (a host-side query of the planner)"""
+    return bool(lib().vlfb_conv_maxpool_fusable(C.byref(d), C.byref(pd)))
+
+
+def conv_run_maxpool(d, pd, A, B, O, O_lo, argmax=None, bias=None, R=None, R_lo=None):
+    """the two-plane FPROP `d` and the max-pool `pd` behind it as ONE launch (vlfb_conv_run_maxpool): O / O_lo are the POOLED
+    planes, argmax the pool's arg-max bytes (None in inference); the un-pooled output is not written"""
+    prof = PROFILE
+    if prof is not None:
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+    fn = lib().vlfb_conv_run_maxpool
+    a = ConvArgs(ptr(A), ptr(B), None, ptr(O), ptr(bias), None, ptr(R), None, None, 0, None, None, ptr(R_lo), ptr(O_lo))
+    args = (C.byref(d), C.byref(pd), C.byref(a), ptr(argmax), stream())   # (a recorded step keeps `a` alive, as in conv_run)
+    rec = tracing()
+    if rec is not None:
+        rec.append((fn, freeze_args(fn, args), "vlfb_conv_run_maxpool"))
+    rc = fn(*args)
+    if prof is not None:
+        e1.record()
+        prof.append((d.mode, conv_flops(d), e0, e1, conv_tag(d), conv_bytes(d, R is not None, False)) + conv_family(d))
+    _check(rc, "vlfb_conv_run_maxpool")
 
 
 def pool_desc(dtype, N, Ti, Hi, Wi, Cc, To, Ho, Wo, k, s, p):
