@@ -444,6 +444,32 @@ int vlfb_bn_bwd(const void* dy, const void* x, const float* gamma, const float* 
                 int64_t workspace_bytes, int dtype, int64_t rows, int64_t C, float grad_scale,
                 vlfb_stream_t stream);
 
+/* SpatialBN of the "mix" path: the same operator on VALUES in the format `xf` -- VLFB_F16PAIR (two fp16 planes, hi at x and lo
+ * rows * C elements behind it; C % 8 == 0) or VLFB_F32 (C % 4 == 0) -- with the residual Sum and the ReLU behind the BN in
+ * its apply pass, and a backward on the gradients the mix backward carries.
+ *   fwd: the moments are those of v = hi + lo (fp32 slab partials about the row-0 pivot, finished in double); training
+ *        (is_test = 0) writes save_mean / save_inv_std and updates the running statistics exactly as vlfb_bn_fwd does,
+ *        is_test = 1 folds the running statistics and writes nothing but y.
+ *        y = a[c] * v + b[c], + residual (NULL: none; format xf, both planes), then max(., 0) when relu != 0; y has the format
+ *        of x.  A pair is written canonical: hi = fp16(y) and fp16(hi + lo) == hi (lo = fp16(y - hi), one fp16 step
+ *        nearer zero where its rounding would tie hi + lo away from hi), so the hi plane is the fp16 copy of the values and,
+ *        behind a ReLU, its mask (lo == 0 wherever hi == 0).
+ *   bwd: x in format xf (both planes are read: xhat = ((hi - mean) + lo) * inv_std); the gradient operand has the type
+ *        gt = VLFB_F16 or VLFB_F32, and with VLFB_F16 an optional low term dy_lo (NULL: none): g = dy + dy_lo.  Sums in fp32
+ *        slab partials, finished in double; dgamma / dbeta fp32, times grad_scale (either may be NULL); dx in type gt (one
+ *        term; NULL: parameter gradients only).  No masking: dy is the finished (already masked) output gradient.
+ * y may alias x or residual, dx may alias dy.  workspace: vlfb_bn_mix_workspace_bytes(xf, rows, C) bytes (-1: bad arguments).
+ * Ordered two-stage reductions, no atomics: two runs give the same bits. */
+int64_t vlfb_bn_mix_workspace_bytes(int xf, int64_t rows, int64_t C);
+int vlfb_bn_fwd_mix(const void* x, void* y, const void* residual, const float* gamma, const float* beta,
+                    float* running_mean, float* running_var, float* save_mean, float* save_inv_std, void* workspace,
+                    int64_t workspace_bytes, int xf, int64_t rows, int64_t C, float eps, float momentum, int is_test,
+                    int relu, vlfb_stream_t stream);
+int vlfb_bn_bwd_mix(const void* dy, const void* dy_lo, const void* x, const float* gamma, const float* save_mean,
+                    const float* save_inv_std, void* dx, float* dgamma, float* dbeta, void* workspace,
+                    int64_t workspace_bytes, int xf, int gt, int64_t rows, int64_t C, float grad_scale,
+                    vlfb_stream_t stream);
+
 /* Precise BN (lib/utils/bn_helper.py): before a checkpoint or an evaluation the running statistics of every SpatialBN
  * layer are replaced by the average of the batch statistics of a number of training batches.  All three entry points
  * read one layer table in DEVICE memory, `layers` records of vlfb_bn_layer; a layer's channels occupy

@@ -829,6 +829,8 @@ class AttentionStep(Step):
         self.inputs, self.outputs = [theta, phi, g], [out]
         self.aux_outputs = [prob]
 
+    P32_MAX_COLS = 2048           # the longest row vlfb_softmax_bwd_p32 keeps in registers
+
     def name(self):
         return "attention:" + self.out.name
 
@@ -879,6 +881,9 @@ class AttentionStep(Step):
         # "mix": dP = dY . g^T as split-bf16 products on fp32 operands (dY through a cast) and the softmax backward on the
         # fp32 probabilities -- what follows cancels the part of dP that is common to a row
         self.precise = bool(eng.mix and eng.MIX_NL_F32)
+        # ... where vlfb_softmax_bwd_p32 takes the row (whole float4 chunks, at most P32_MAX_COLS keys); a longer key axis -- the
+        # ungrouped res3 block of a SpatialBN graph at 224^2: 3136 keys -- keeps the fp32 dP and reads the fp16 copy of P
+        self.p32 = bool(self.precise and L2 % 4 == 0 and L2 <= self.P32_MAX_COLS)
         # split math: the B operands (phi, g^T, g, phi^T) are activations, expanded into bf16 term planes by
         # vlfb_split_planes right before the product that reads them (3 planes forward, 2 backward; "mix": split forward
         # products, native fp16 backward)
@@ -1057,7 +1062,7 @@ class AttentionStep(Step):
         if self.fused_bwd:
             hip.call("vlfb_attn_scores_bwd", hip.ptr(dY), self.g.bptr(), hip.ptr(P), hip.ptr(dS), eng.bcode, B, L1, L2, Ci,
                      self.scale * self.ds_scale)
-        elif self.precise:
+        elif self.p32:
             hip.call("vlfb_softmax_bwd_p32", hip.ptr(dP), self.prob.ptr(), hip.ptr(dS), eng.bcode, B * L1, L2,
                      self.scale * self.ds_scale)
         else:
@@ -1120,7 +1125,9 @@ class ReluStep(Step):
 class BNStep(Step):
     """SpatialBN (model_builder_video.py:186-190, resnet_video.py:185-188, nonlocal_helper.py:147-151): batch statistics of
     THIS GPU's rows in a training net (and the running statistics updated), the running statistics in a test / val net.
-    vlfb_bn_fwd / vlfb_bn_bwd; scale and bias are trained, `_rm` / `_riv` are computed parameters."""
+    vlfb_bn_fwd / vlfb_bn_bwd; scale and bias are trained, `_rm` / `_riv` are computed parameters.
+    "mix": vlfb_bn_fwd_mix / vlfb_bn_bwd_mix on two-plane (or fp32) values, with the ReLU / residual Sum behind the BN in its
+    apply pass and the fp16 (two-term) or fp32 gradient of the slot it writes; `save` keeps its layout (mean, inverse std)."""
 
     def __init__(self, eng, x, out, sname, bname, rmname, rvname, eps, momentum, is_test):
         Step.__init__(self, eng)
@@ -1128,6 +1135,9 @@ class BNStep(Step):
         self.sname, self.bname, self.rmname, self.rvname = sname, bname, rmname, rvname
         self.eps, self.momentum, self.is_test = float(eps), float(momentum), int(bool(is_test))
         self.inputs, self.outputs = [x], [out]
+        # "mix" only: the ReLU and the residual Sum behind the BN run in its apply pass (Lowering.lower_Relu / lower_Sum)
+        self.relu = False
+        self.residual = None
 
     def param_names(self):
         return (self.sname, self.bname)
@@ -1137,19 +1147,41 @@ class BNStep(Step):
 
     def setup(self):
         eng = self.eng
-        if eng.mix:
-            raise NotImplementedError("SpatialBN graphs are not built for the 'mix' dtype (use 'split' / 'fp32' / 16-bit)")
         self.rows, self.C = self.x.rows, self.x.C
         self.params = [n for n in (self.sname, self.bname) if eng.is_trainable(n)]
+        self.save = None if self.is_test else torch.empty(2 * self.C, device=eng.device, dtype=torch.float32)
+        if eng.mix:
+            # vlfb_bn_fwd_mix / vlfb_bn_bwd_mix: input, residual and output in ONE value format -- two fp16 planes
+            # (Engine._plan_pairs) or fp32; the gradient in the type of the slot this step writes (fp16, or fp32: Blob.grad_f32)
+            self.xf = hip.F16PAIR if self.x.root.pair else hip.F32
+            fmts = [bool(b.root.pair) for b in (self.x, self.out) + ((self.residual,) if self.residual is not None else ())]
+            if len(set(fmts)) != 1 or self.C % (8 if self.x.root.pair else 4) or self.x.root.kind != "act":
+                raise NotImplementedError("SpatialBN %s on 'mix': input / residual / output formats %r with %d channels"
+                                          % (self.out.name, fmts, self.C))
+            gblob = self.x if self.grad_inputs() else self.out
+            self.gt = hip.F32 if gblob.root.grad_f32 else hip.F16
+            nbytes = hip.lib().vlfb_bn_mix_workspace_bytes(self.xf, self.rows, self.C)
+            if nbytes <= 0:
+                raise hip.VlfbError("vlfb_bn_mix_workspace_bytes(%d, %d, %d)" % (self.xf, self.rows, self.C))
+            self.ws = torch.empty(nbytes // 4, device=eng.device, dtype=torch.float32)
+            if self.gt == hip.F32 and self.grad_inputs():
+                eng.need_scratch_f32(self.x.numel)            # GradSlot's add path for an fp32 slot
+            return
+        assert not self.relu and self.residual is None
         nbytes = hip.query_workspace(hip.WS_BN, (eng.code, self.rows, self.C))
         self.ws = torch.empty(nbytes // 4, device=eng.device, dtype=torch.float32)
-        self.save = None if self.is_test else torch.empty(2 * self.C, device=eng.device, dtype=torch.float32)
 
     def fwd(self):
         eng = self.eng
         P = eng.param_tensor
         mean = hip.ptr(self.save) if self.save is not None else None
         istd = hip.ptr(self.save) + 4 * self.C if self.save is not None else None
+        if eng.mix:
+            hip.call("vlfb_bn_fwd_mix", self.x.ptr(), self.out.ptr(), self.residual.ptr() if self.residual is not None else None,
+                     hip.ptr(P(self.sname)), hip.ptr(P(self.bname)), hip.ptr(P(self.rmname)), hip.ptr(P(self.rvname)), mean, istd,
+                     hip.ptr(self.ws), self.ws.numel() * 4, self.xf, self.rows, self.C, self.eps, self.momentum, self.is_test,
+                     int(self.relu))
+            return
         hip.call("vlfb_bn_fwd", self.x.ptr(), self.out.ptr(), hip.ptr(P(self.sname)), hip.ptr(P(self.bname)),
                  hip.ptr(P(self.rmname)), hip.ptr(P(self.rvname)), mean, istd, hip.ptr(self.ws), self.ws.numel() * 4,
                  eng.code, self.rows, self.C, self.eps, self.momentum, self.is_test)
@@ -1160,12 +1192,36 @@ class BNStep(Step):
         g = self.out_grad()
         dgamma = hip.ptr(eng.grad_tensor(self.sname)) if eng.is_trainable(self.sname) else None
         dbeta = hip.ptr(eng.grad_tensor(self.bname)) if eng.is_trainable(self.bname) else None
+        if eng.mix:
+            return self._bwd_mix(g, dgamma, dbeta)
 
         def launch(out, add=None, mask=None):
             hip.call("vlfb_bn_bwd", hip.ptr(g), self.x.ptr(), hip.ptr(eng.param_tensor(self.sname)), hip.ptr(self.save),
                      hip.ptr(self.save) + 4 * self.C, hip.ptr(out), dgamma, dbeta, hip.ptr(self.ws), self.ws.numel() * 4,
                      eng.code, self.rows, self.C, 1.0)
         if self.grad_inputs():
+            self.x.root.slot.contribute(launch, supports_add=False, supports_mask=False)
+        elif dgamma is not None or dbeta is not None:
+            launch(None)
+
+    def _bwd_mix(self, g, dgamma, dbeta):
+        """g: the finished (masked) gradient of the fused output.  It is the gradient of the residual operand as it is (an
+        alias, low term included: AddStep.bwd), and the gradient operand of vlfb_bn_bwd_mix."""
+        eng = self.eng
+        g_lo = self.out.root.slot.value_lo()
+        if self.residual is not None and self.residual.needs_grad and not self.residual.detached:
+            self.residual.root.slot.contribute_alias(g, g_lo)
+        has_dx = bool(self.grad_inputs())
+        if has_dx and bool(self.out.root.grad_f32) != bool(self.x.root.grad_f32):
+            g, g_lo = self.g_as(g, self.out, self.x), None        # (the gradient changes its type across this step)
+        if self.gt != hip.F16:
+            g_lo = None
+
+        def launch(out, add=None, mask=None):
+            hip.call("vlfb_bn_bwd_mix", hip.ptr(g), hip.ptr(g_lo), self.x.ptr(), hip.ptr(eng.param_tensor(self.sname)),
+                     hip.ptr(self.save), hip.ptr(self.save) + 4 * self.C, hip.ptr(out), dgamma, dbeta, hip.ptr(self.ws),
+                     self.ws.numel() * 4, self.xf, self.gt, self.rows, self.C, 1.0)
+        if has_dx:
             self.x.root.slot.contribute(launch, supports_add=False, supports_mask=False)
         elif dgamma is not None or dbeta is not None:
             launch(None)
@@ -1609,6 +1665,25 @@ class Lowering(object):
                 self.add_step(st)
                 self.env[out_name] = out
                 return j + 1
+        # "mix": ... or into the apply pass of the SpatialBN that produced one operand (first operand preferred: in a projection
+        # block the second BN stays as it is, its output is the residual)
+        for cand, other, ref in ((a, b, ins[0]), (b, a, ins[1])):
+            st = cand.producer
+            if (self.eng.mix and isinstance(st, BNStep) and cand is st.out and not st.relu and st.residual is None
+                    and self.readers.get(ref, 0) == 1 and cand.shape == other.shape and other.caxis == cand.caxis):
+                self.steps.remove(st)
+                cand.dead = True
+                st.residual = other
+                st.relu = relu
+                st.inputs = [st.x, other]
+                out = self.new_blob(out_name, cand.shape, cand.caxis)
+                out.relu = relu
+                out.needs_grad = True
+                st.out = out
+                st.outputs = [out]
+                self.add_step(st)
+                self.env[out_name] = out
+                return j + 1
         out = self.new_blob(out_name, a.shape, a.caxis)
         out.relu = relu
         out.needs_grad = a.needs_grad or b.needs_grad
@@ -1619,6 +1694,21 @@ class Lowering(object):
     def lower_Relu(self, i):
         op, ins, outs = self.ssa[i]
         x = self.get(op.inputs[0])
+        st = x.producer
+        if (self.eng.mix and isinstance(st, BNStep) and x is st.out and not st.relu and st.residual is None
+                and self.readers.get(ins[0], 0) == 1):
+            # "mix": the ReLU runs in the apply pass of the SpatialBN that produced its input (as lower_Sum folds)
+            self.steps.remove(st)
+            x.dead = True
+            st.relu = True
+            out = self.new_blob(op.outputs[0], x.shape, x.caxis)
+            out.relu = True
+            out.needs_grad = True
+            st.out = out
+            st.outputs = [out]
+            self.add_step(st)
+            self.env[op.outputs[0]] = out
+            return i + 1
         out = self.new_blob(op.outputs[0], x.shape, x.caxis)
         out.relu = True
         out.needs_grad = x.needs_grad
@@ -2356,10 +2446,11 @@ class Engine(object):
     PAIR_SCORES = os.environ.get("VLFB_PAIR_SCORES", "1") != "0"                # (A/B switch: theta / phi as two planes)
 
     def _plan_pairs(self):
-        """Which activations are stored as two fp16 planes (Blob.pair).  A blob qualifies when a conv or a max pool over a
-        two-plane blob produces it and EVERY consumer can read the format: a conv (as its input: plain rows or whole 32-channel
-        k-tiles; or as the residual of its epilogue), a max pool (whose output then qualifies in turn), an average pool (fp32
-        out: the head).  The formats of a conv's residual and output, and of a max pool's input and output, are tied; a conv
+        """Which activations are stored as two fp16 planes (Blob.pair).  A blob qualifies when a conv, or a max pool or a
+        SpatialBN over a two-plane blob produces it and EVERY consumer can read the format: a conv (as its input: plain rows or
+        whole 32-channel k-tiles; or as the residual of its epilogue), a max pool (whose output then qualifies in turn), an
+        average pool (fp32 out: the head), a SpatialBN on "mix" (as its input or as the residual of its apply pass).  The formats
+        of a conv's residual and output, of a max pool's input and output, and of a BN's input, residual and output are tied; a conv
         with a two-plane input and an fp32 output takes no residual.  Everything else -- theta / phi / g and the internals of a
         non-local block, the head, the FBO branch -- stays fp32 and is read by the kernels it was read by before."""
         self.pair_fwd = bool(self.mix and self.MIX_PAIR)
@@ -2375,6 +2466,8 @@ class Engine(object):
             if (isinstance(st, ConvStep) and st.group == 1 and st.out is b and (not b.grad_f32 or self.PAIR_SCORES)) or \
                     (isinstance(st, PoolStep) and st.is_max):
                 cand[id(b)] = b            # (an fp32-gradient conv output -- theta / phi / g -- only survives as theta / phi below)
+            elif isinstance(st, BNStep) and st.out is b and not b.grad_f32:
+                cand[id(b)] = b            # (a SpatialBN over a two-plane input: input, residual and output share the format)
             elif isinstance(st, AttentionStep) and st.theta.shape[2] > 1 and not st.dot and st.out is b and self.PAIR_ATTENTION_OUT:
                 # the attention output of a non-local block: its P . g product writes two planes (split-bf16 launch with a
                 # two-plane output), so the `out` conv behind it is a two-plane conv as well
@@ -2396,6 +2489,8 @@ class Engine(object):
                 p = b.producer
                 if isinstance(p, PoolStep):
                     ok = id(p.x.root) in cand
+                elif isinstance(p, BNStep):
+                    ok = id(p.x.root) in cand and (p.residual is None or id(p.residual.root) in cand)
                 elif isinstance(p, ConvStep) and b.grad_f32:
                     # a conv output with an fp32 gradient slot: only theta / phi of a space-time non-local block (the FBO
                     # head's convs run the split-bf16 backward on fp32 VALUES: they keep fp32 storage)
@@ -2407,6 +2502,9 @@ class Engine(object):
                             ok = ok and id(st.out.root) in cand
                         if st.x.root is b and st.residual is not None and st.residual.root is not b:
                             ok = ok and id(st.residual.root) in cand       # (two-plane input + fp32 residual: no kernel)
+                    elif isinstance(st, BNStep):
+                        # as the input or as the residual of its apply pass: one format for input, residual and output
+                        ok = ok and all(id(q.root) in cand for q in st.inputs + st.outputs) and not b.grad_f32
                     elif isinstance(st, PoolStep):
                         ok = ok and (not st.is_max or id(st.out.root) in cand) and v.caxis == 1 and len(v.shape) == 5
                     elif isinstance(st, AttentionStep) and st.theta.shape[2] > 1 and not st.dot and self.PAIR_SCORES and \
@@ -2529,7 +2627,8 @@ class Engine(object):
             # the residual stream: a blob that is the identity operand of a conv's residual Sum receives that conv's output
             # gradient as an alias and adds its own branch to it (GradSlot.two_term)
             for st in self.bwd_steps:
-                if isinstance(st, ConvStep) and st.residual is not None and st.residual.needs_grad and not st.residual.detached:
+                # (a SpatialBN with the residual Sum in its apply pass hands the gradient on in the same way: BNStep._bwd_mix)
+                if isinstance(st, (ConvStep, BNStep)) and st.residual is not None and st.residual.needs_grad and not st.residual.detached:
                     r = st.residual.root
                     if r.kind == "act" and not r.grad_f32 and r.slot.expected > 1:
                         r.slot.two_term = True

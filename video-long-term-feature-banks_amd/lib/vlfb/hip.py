@@ -222,7 +222,11 @@ _SIGS = {
     "vlfb_bn_workspace_bytes": (_I64, [C.c_int, _I64, _I64]),
     "vlfb_bn_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, _I64, _I64, C.c_float, C.c_float, C.c_int, _P]),
     "vlfb_bn_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, _I64, _I64, C.c_float, _P]),
-    "vlfb_bn_precise_accumulate": (C.c_int, [_P, C.c_int, C.c_float, _P, _P, _P]),
+    "vlfb_bn_mix_workspace_bytes": (_I64, [C.c_int, _I64, _I64]),
+    "vlfb_bn_fwd_mix": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, _I64, _I64, C.c_float, C.c_float,
+                                  C.c_int, C.c_int, _P]),
+    "vlfb_bn_bwd_mix": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, C.c_int, C.c_int, _I64, _I64, C.c_float, _P]),
+    "vlfb_bn_precise_accumulate":(C.c_int, [_P, C.c_int, C.c_float, _P, _P, _P]),
     "vlfb_bn_precise_finalize": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P]),
     "vlfb_bn_precise_update": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "vlfb_layernorm_fwd": (C.c_int, [_P, _P, _P, C.c_int, _I64, _I64, C.c_float, _P]),
