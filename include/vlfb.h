@@ -325,6 +325,9 @@ typedef struct vlfb_pool_desc {
   int32_t To, Ho, Wo;
   int32_t kt, kh, kw, st, sh, sw, pt, ph, pw;
 } vlfb_pool_desc;
+/* Every pool entry point checks the descriptor against itself before anything is launched (VLFB_ERR_ARG, the message names
+ * the dimension t / h / w): extents, kernels and strides positive; 0 <= pad < kernel; for max pools the last window has a tap
+ * inside the input, (To-1)*st - pt <= Ti-1; for average pools (pad 0) it lies inside the input, (To-1)*st + kt <= Ti. */
 /* bytes per arg-max element: 1 (window <= 255 taps) or 2 (the FBO-max head pools 300 bank rows) */
 int vlfb_pool_argmax_bytes(const vlfb_pool_desc* d);
 /* y[N,To,Ho,Wo,C]; argmax (tap index inside the window, first maximum in t,h,w scan order; element
@@ -341,6 +344,19 @@ int vlfb_maxpool_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax
  * kt*kh*kw / (st*sh*sw) times less mask traffic. */
 int vlfb_maxpool_relu_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax, const void* y, void* dx,
                           vlfb_stream_t stream);
+/* Which kernel vlfb_maxpool_bwd (has_y = 0) / vlfb_maxpool_relu_bwd (has_y = 1, has_add = has_mask = 0) runs for this
+ * descriptor, as text in `buf` (at least 64 bytes); launches nothing and needs no GPU.  The launch code switches on the same
+ * decision, so the route a test names is the route that runs.  The rule, in this order:
+ *   1. a two-byte arg-max (window > 255 taps), or >= 2^31 input rows (N*Ti*Hi) or pooled positions: "generic u16 bf16" / "generic u8 bf16"
+ *   2. window 1x3x3, stride 1x2x2, pt = 0, To = Ti, neither add nor mask: with row_bytes = Wo * C * (element bytes + 1) and
+ *      R = min(3, 65536 / row_bytes - 2), when R >= 2 the band kernel (2R input rows per workgroup, R + 2 pooled rows in LDS,
+ *      bands = ceil(Hi / 2R) workgroups per frame): "band f16 R=3 bands=5"
+ *   3. window / stride 1x3x3 / 1x2x2, 2x1x1 / 2x1x1 or 1x2x2 / 1x2x2 (any pads): the row kernel compiled for that window,
+ *      "fixed 1x3x3/1x2x2 f32"
+ *   4. anything else: "generic u8 f32"
+ * " ymask" is appended when has_y.  All routes give identical bits: the same fp32 sum over the covering windows in ascending
+ * (to, ho, wo) order, then add, then mask, then one rounding.  The descriptor is checked as by vlfb_maxpool_bwd. */
+int vlfb_maxpool_bwd_describe(const vlfb_pool_desc* d, int has_add, int has_mask, int has_y, char* buf, int64_t buf_bytes);
 /* A two-plane FPROP launch (math VLFB_MATH_F16X3, out_dtype VLFB_F16) and the max-pool behind it in ONE launch, for a conv
  * output that nothing but the pool reads (pool2 behind res2's last conv: resnet_video.py:229-236): the epilogue forms the two
  * planes every output row would have stored, takes the window maximum on hi + lo with a strict > in tap order -- what

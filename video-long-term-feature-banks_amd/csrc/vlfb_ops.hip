@@ -846,51 +846,83 @@ __global__ __launch_bounds__(256) void maxpool_bwd_band_kernel(const T* __restri
   }
 }
 
-// launches the fixed-shape kernel when the window is one of the compiled shapes (one-byte arg-max); false = use the generic one
-template <typename T>
-bool launch_maxpool_bwd_fixed(const PoolP& p, const void* dy, const void* argmax, void* dx, const void* add, const void* mask,
-                              const void* ymask, hipStream_t s) {
-  const long long rows = (long long)p.N * p.Ti * p.Hi;
-  if (rows >= (1ll << 31) || (long long)p.N * p.To * p.Ho * p.Wo >= (1ll << 31)) return false;
-  const dim3 grid((unsigned)rows), block(128);
+// Which kernel the max-pool backward runs: ONE pure host function, read by the launch code below and printed by
+// vlfb_maxpool_bwd_describe (include/vlfb.h states the rule), so the route a test names is the route that runs.
+enum class PoolBwdKind : int { generic, fixed, band };
+struct PoolBwdRoute {
+  PoolBwdKind kind;
+  int window;          // fixed: index into kPoolFixedWindows
+  int R, bands;        // band: input-row pairs per workgroup, workgroups per frame
+  bool ymask, wide;    // the pooled values are the ReLU mask; two-byte arg-max
+};
+struct PoolWindow { int kt, kh, kw, st, sh, sw; };
+constexpr PoolWindow kPoolFixedWindows[3] = {{1, 3, 3, 1, 2, 2}, {2, 1, 1, 2, 1, 1}, {1, 2, 2, 1, 2, 2}};
+PoolBwdRoute maxpool_bwd_route(const PoolP& p, int elem_bytes, int argmax_bytes, bool has_add, bool has_mask, bool has_y) {
+  PoolBwdRoute r = {PoolBwdKind::generic, -1, 0, 0, has_y, argmax_bytes == 2};
+  if (r.wide) return r;
+  // (the fixed-shape kernels index rows and pooled positions with 32 bits)
+  if ((long long)p.N * p.Ti * p.Hi >= (1ll << 31) || (long long)p.N * p.To * p.Ho * p.Wo >= (1ll << 31)) return r;
   // (with a residual operand and a ReLU mask streamed beside it the row kernel is the faster one: 271 vs 357 us)
-  if (p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 2 && p.sw == 2 && p.pt == 0 && p.To == p.Ti && !add &&
-      !mask) {
+  if (p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 2 && p.sw == 2 && p.pt == 0 && p.To == p.Ti && !has_add &&
+      !has_mask) {
     // band kernel: as many input-row pairs per workgroup as 64 KB of LDS hold pooled rows for (R + 2 rows staged)
-    const long long row_bytes = (long long)p.Wo * p.C * (sizeof(T) + 1);
+    const long long row_bytes = (long long)p.Wo * p.C * (elem_bytes + 1);
     // R = 3: measured 226 us at R = 2 and 3, 259 us at R = 4 (two 64 KB workgroups per CU leave the load and the store
     // phases of a CU unbalanced) against 285 us for the row kernel, pool1 of the 8-clip step in isolation
     const int R = (int)std::min<long long>(3, 65536 / row_bytes - 2);
     if (R >= 2) {
       const int bands = (p.Hi + 2 * R - 1) / (2 * R);
-      const long long wgs = (long long)p.N * p.Ti * bands;
-      const size_t lds = (size_t)(R + 2) * row_bytes;
-      if (wgs < (1ll << 31)) {
-        if (ymask)
-          hipLaunchKernelGGL((maxpool_bwd_band_kernel<T, true>), dim3((unsigned)wgs), dim3(256), lds, s, (const T*)dy,
-                             (const uint8_t*)argmax, (T*)dx, (const T*)add, (const T*)mask, p, (const T*)ymask, R, bands);
-        else
-          hipLaunchKernelGGL((maxpool_bwd_band_kernel<T, false>), dim3((unsigned)wgs), dim3(256), lds, s, (const T*)dy,
-                             (const uint8_t*)argmax, (T*)dx, (const T*)add, (const T*)mask, p, (const T*)ymask, R, bands);
-        return true;
+      if ((long long)p.N * p.Ti * bands < (1ll << 31)) {
+        r.kind = PoolBwdKind::band; r.R = R; r.bands = bands;
+        return r;
       }
     }
   }
-#define VLFB_POOL_FIXED(KT_, KH_, KW_, ST_, SH_, SW_)                                                                      \
-  if (p.kt == KT_ && p.kh == KH_ && p.kw == KW_ && p.st == ST_ && p.sh == SH_ && p.sw == SW_) {                           \
+  for (int i = 0; i < 3; ++i) {
+    const PoolWindow& w = kPoolFixedWindows[i];
+    if (p.kt == w.kt && p.kh == w.kh && p.kw == w.kw && p.st == w.st && p.sh == w.sh && p.sw == w.sw) {
+      r.kind = PoolBwdKind::fixed; r.window = i;
+      return r;
+    }
+  }
+  return r;
+}
+
+// launches the band / fixed-shape kernel the route names (one-byte arg-max); the generic kernel is the caller's
+template <typename T>
+void launch_maxpool_bwd_fixed(const PoolBwdRoute& r, const PoolP& p, const void* dy, const void* argmax, void* dx, const void* add,
+                              const void* mask, const void* ymask, hipStream_t s) {
+  if (r.kind == PoolBwdKind::band) {
+    const int R = r.R, bands = r.bands;
+    const long long row_bytes = (long long)p.Wo * p.C * (sizeof(T) + 1);
+    const long long wgs = (long long)p.N * p.Ti * bands;
+    const size_t lds = (size_t)(R + 2) * row_bytes;
+    if (ymask)
+      hipLaunchKernelGGL((maxpool_bwd_band_kernel<T, true>), dim3((unsigned)wgs), dim3(256), lds, s, (const T*)dy,
+                         (const uint8_t*)argmax, (T*)dx, (const T*)add, (const T*)mask, p, (const T*)ymask, R, bands);
+    else
+      hipLaunchKernelGGL((maxpool_bwd_band_kernel<T, false>), dim3((unsigned)wgs), dim3(256), lds, s, (const T*)dy,
+                         (const uint8_t*)argmax, (T*)dx, (const T*)add, (const T*)mask, p, (const T*)ymask, R, bands);
+    return;
+  }
+  const dim3 grid((unsigned)((long long)p.N * p.Ti * p.Hi)), block(128);
+#define VLFB_POOL_FIXED(I_, KT_, KH_, KW_, ST_, SH_, SW_)                                                                  \
+  static_assert(kPoolFixedWindows[I_].kt == KT_ && kPoolFixedWindows[I_].kh == KH_ && kPoolFixedWindows[I_].kw == KW_ &&   \
+                kPoolFixedWindows[I_].st == ST_ && kPoolFixedWindows[I_].sh == SH_ && kPoolFixedWindows[I_].sw == SW_,     \
+                "the compiled windows are the routed windows");                                                           \
+  if (r.window == I_) {                                                                                                  \
     if (ymask)                                                                                                           \
       hipLaunchKernelGGL((maxpool_bwd_fixed_kernel<T, KT_, KH_, KW_, ST_, SH_, SW_, true>), grid, block, 0, s,           \
                          (const T*)dy, (const uint8_t*)argmax, (T*)dx, (const T*)add, (const T*)mask, p, (const T*)ymask); \
     else                                                                                                                 \
       hipLaunchKernelGGL((maxpool_bwd_fixed_kernel<T, KT_, KH_, KW_, ST_, SH_, SW_, false>), grid, block, 0, s,          \
                          (const T*)dy, (const uint8_t*)argmax, (T*)dx, (const T*)add, (const T*)mask, p, (const T*)ymask); \
-    return true;                                                                                                         \
+    return;                                                                                                              \
   }
-  VLFB_POOL_FIXED(1, 3, 3, 1, 2, 2)
-  VLFB_POOL_FIXED(2, 1, 1, 2, 1, 1)
-  VLFB_POOL_FIXED(1, 2, 2, 1, 2, 2)
+  VLFB_POOL_FIXED(0, 1, 3, 3, 1, 2, 2)
+  VLFB_POOL_FIXED(1, 2, 1, 1, 2, 1, 1)
+  VLFB_POOL_FIXED(2, 1, 2, 2, 1, 2, 2)
 #undef VLFB_POOL_FIXED
-  return false;
 }
 
 template <typename T>
@@ -1215,12 +1247,31 @@ PoolP to_poolp(const vlfb_pool_desc* d) {
   p.pt = d->pt; p.ph = d->ph; p.pw = d->pw;
   return p;
 }
-int check_pool(const vlfb_pool_desc* d) {
+// Descriptor checks shared by every pool entry point, before anything is launched.  The kernels trust the descriptor: the
+// average pools read hi = ho*sh + b with no bounds test, the max-pool forward would write -inf / tap 0 for a window with no
+// valid tap -- so an output extent the input does not carry is an argument error here, with the dimension named.
+int check_pool(const vlfb_pool_desc* d, bool is_max) {
   VLFB_REQUIRE(d->dtype == VLFB_F32 || is16(d->dtype) || d->dtype == VLFB_F16PAIR, "pool: bad dtype");
   const int v = d->dtype == VLFB_F32 ? 4 : 8;
+  VLFB_REQUIRE(d->N > 0 && d->C > 0, "pool: N=%d and C=%d must be positive", d->N, d->C);
   VLFB_REQUIRE(d->C % v == 0, "pool: C=%d must be a multiple of %d", d->C, v);
-  VLFB_REQUIRE(d->kt * d->kh * d->kw <= 65535, "pool: window too large for a 16-bit argmax");
-  VLFB_REQUIRE(d->N > 0 && d->To > 0 && d->Ho > 0 && d->Wo > 0, "pool: empty output");
+  const struct { const char* n; int in, out, k, s, p; } dims[3] = {{"t", d->Ti, d->To, d->kt, d->st, d->pt},
+                                                                   {"h", d->Hi, d->Ho, d->kh, d->sh, d->ph},
+                                                                   {"w", d->Wi, d->Wo, d->kw, d->sw, d->pw}};
+  for (const auto& a : dims) {
+    VLFB_REQUIRE(a.in > 0 && a.out > 0 && a.k > 0 && a.s > 0, "pool: dimension %s: input %d, output %d, kernel %d and stride %d must be positive",
+                 a.n, a.in, a.out, a.k, a.s);
+    VLFB_REQUIRE(a.p >= 0 && a.p < a.k, "pool: dimension %s: pad %d must be in [0, kernel %d)", a.n, a.p, a.k);
+    if (is_max)
+      VLFB_REQUIRE((long long)(a.out - 1) * a.s - a.p <= a.in - 1,
+                   "pool: dimension %s: the last of %d windows (stride %d, pad %d) has no tap inside the input extent %d", a.n, a.out,
+                   a.s, a.p, a.in);
+    else
+      VLFB_REQUIRE((long long)(a.out - 1) * a.s + a.k <= a.in,
+                   "pool: dimension %s: the last of %d windows (kernel %d, stride %d) leaves the input extent %d", a.n, a.out, a.k,
+                   a.s, a.in);
+  }
+  VLFB_REQUIRE((long long)d->kt * d->kh * d->kw <= 65535, "pool: window too large for a 16-bit argmax");
   return VLFB_OK;
 }
 
@@ -1354,7 +1405,7 @@ extern "C" int vlfb_pool_argmax_bytes(const vlfb_pool_desc* d) {
 }
 extern "C" int vlfb_maxpool_fwd(const vlfb_pool_desc* d, const void* x, void* y, void* argmax,
                                 vlfb_stream_t stream) {
-  int rc = check_pool(d);
+  int rc = check_pool(d, true);
   if (rc) return rc;
   VLFB_REQUIRE(x && y, "maxpool_fwd: null pointer");
   PoolP p = to_poolp(d);
@@ -1386,10 +1437,11 @@ static int maxpool_bwd_impl(const vlfb_pool_desc* d, const void* dy, const void*
   const int v = d->dtype == VLFB_F32 ? 4 : 8;
   const bool wide = vlfb_pool_argmax_bytes(d) == 2;
   int grid = grid_for((long long)p.N * p.Ti * p.Hi * p.Wi * (p.C / v), 256);
-  bool fixed = false;
+  const PoolBwdRoute route = maxpool_bwd_route(p, d->dtype == VLFB_F32 ? 4 : 2, wide ? 2 : 1, add != nullptr, mask != nullptr, y != nullptr);
+  const bool fixed = route.kind != PoolBwdKind::generic;
   if (!with_elem(d->dtype, [&](auto t) {
         using T = decltype(t);
-        if (!wide && (fixed = launch_maxpool_bwd_fixed<T>(p, dy, argmax, dx, add, mask, y, s))) return;
+        if (fixed) return launch_maxpool_bwd_fixed<T>(route, p, dy, argmax, dx, add, mask, y, s);
         with_argmax(wide, [&](auto i) {
           using I = decltype(i);
           hipLaunchKernelGGL((pool_bwd_kernel<T, true, I>), dim3(grid), dim3(256), 0, s, (const T*)dy, (const I*)argmax, (T*)dx, (const T*)add,
@@ -1401,20 +1453,40 @@ static int maxpool_bwd_impl(const vlfb_pool_desc* d, const void* dy, const void*
 }
 extern "C" int vlfb_maxpool_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax,
                                 void* dx, const void* add, const void* mask, vlfb_stream_t stream) {
-  int rc = check_pool(d);
+  int rc = check_pool(d, true);
   if (rc) return rc;
   VLFB_REQUIRE(dy && argmax && dx, "maxpool_bwd: null pointer");
   return maxpool_bwd_impl(d, dy, argmax, dx, add, mask, nullptr, (hipStream_t)stream, "maxpool_bwd (fixed window)", "maxpool_bwd");
 }
 extern "C" int vlfb_maxpool_relu_bwd(const vlfb_pool_desc* d, const void* dy, const void* argmax, const void* y,
                                      void* dx, vlfb_stream_t stream) {
-  int rc = check_pool(d);
+  int rc = check_pool(d, true);
   if (rc) return rc;
   VLFB_REQUIRE(dy && argmax && dx && y, "maxpool_relu_bwd: null pointer");
   return maxpool_bwd_impl(d, dy, argmax, dx, nullptr, nullptr, y, (hipStream_t)stream, "maxpool_relu_bwd (fixed window)", "maxpool_relu_bwd");
 }
+extern "C" int vlfb_maxpool_bwd_describe(const vlfb_pool_desc* d, int has_add, int has_mask, int has_y, char* buf, int64_t buf_bytes) {
+  VLFB_REQUIRE(d && buf && buf_bytes >= 64, "maxpool_bwd_describe: buf of at least 64 bytes");
+  int rc = check_pool(d, true);
+  if (rc) return rc;
+  VLFB_REQUIRE(d->dtype == VLFB_F32 || is16(d->dtype), "pool: bad dtype");        // (VLFB_F16PAIR: the backward runs on one plane)
+  VLFB_REQUIRE(!(has_y && (has_add || has_mask)), "maxpool_bwd_describe: y (vlfb_maxpool_relu_bwd) comes without add and mask");
+  const PoolBwdRoute r = maxpool_bwd_route(to_poolp(d), d->dtype == VLFB_F32 ? 4 : 2, vlfb_pool_argmax_bytes(d), has_add != 0, has_mask != 0,
+                                           has_y != 0);
+  const char* dt = d->dtype == VLFB_F32 ? "f32" : d->dtype == VLFB_F16 ? "f16" : "bf16";
+  const char* ym = r.ymask ? " ymask" : "";
+  if (r.kind == PoolBwdKind::band) {
+    snprintf(buf, (size_t)buf_bytes, "band %s R=%d bands=%d%s", dt, r.R, r.bands, ym);
+  } else if (r.kind == PoolBwdKind::fixed) {
+    const PoolWindow& w = kPoolFixedWindows[r.window];
+    snprintf(buf, (size_t)buf_bytes, "fixed %dx%dx%d/%dx%dx%d %s%s", w.kt, w.kh, w.kw, w.st, w.sh, w.sw, dt, ym);
+  } else {
+    snprintf(buf, (size_t)buf_bytes, "generic %s %s%s", r.wide ? "u16" : "u8", dt, ym);
+  }
+  return VLFB_OK;
+}
 extern "C" int vlfb_avgpool_fwd(const vlfb_pool_desc* d, const void* x, void* y, vlfb_stream_t stream) {
-  int rc = check_pool(d);
+  int rc = check_pool(d, false);
   if (rc) return rc;
   VLFB_REQUIRE(x && y, "avgpool_fwd: null pointer");
   VLFB_REQUIRE(d->pt == 0 && d->ph == 0 && d->pw == 0, "avgpool: padding is not supported (none in the reference)");
@@ -1446,7 +1518,7 @@ extern "C" int vlfb_avgpool_fwd(const vlfb_pool_desc* d, const void* x, void* y,
 }
 extern "C" int vlfb_avgpool_bwd(const vlfb_pool_desc* d, const void* dy, void* dx, const void* add,
                                 const void* mask, vlfb_stream_t stream) {
-  int rc = check_pool(d);
+  int rc = check_pool(d, false);
   if (rc) return rc;
   VLFB_REQUIRE(dy && dx, "avgpool_bwd: null pointer");
   VLFB_REQUIRE(d->pt == 0 && d->ph == 0 && d->pw == 0, "avgpool: padding is not supported");
@@ -1517,7 +1589,7 @@ __global__ void avgpool_bwd_two_term_kernel(const float* __restrict__ dy, T* __r
 
 extern "C" int vlfb_avgpool_bwd_two_term(const vlfb_pool_desc* d, const float* dy, void* dx_hi, void* dx_lo, const void* mask,
                                          vlfb_stream_t stream) {
-  int rc = check_pool(d);
+  int rc = check_pool(d, false);
   if (rc) return rc;
   VLFB_REQUIRE(dy && dx_hi && dx_lo, "avgpool_bwd_two_term: null pointer");
   VLFB_REQUIRE(d->pt == 0 && d->ph == 0 && d->pw == 0, "avgpool: padding is not supported");

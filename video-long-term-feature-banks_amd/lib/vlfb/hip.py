@@ -204,6 +204,7 @@ _SIGS = {
     "vlfb_maxpool_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P]),
     "vlfb_maxpool_bwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P, _P, _P]),
     "vlfb_maxpool_relu_bwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P, _P, _P]),
+    "vlfb_maxpool_bwd_describe": (C.c_int, [C.POINTER(PoolDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, _I64]),
     "vlfb_conv_maxpool_fusable": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(PoolDesc)]),
     "vlfb_conv_run_maxpool": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(PoolDesc), C.POINTER(ConvArgs), _P, _P]),
     "vlfb_avgpool_fwd": (C.c_int, [C.POINTER(PoolDesc), _P, _P, _P]),
@@ -537,6 +538,15 @@ def pool_desc(dtype, N, Ti, Hi, Wi, Cc, To, Ho, Wo, k, s, p):
     d.st, d.sh, d.sw = s
     d.pt, d.ph, d.pw = p
     return d
+
+
+def maxpool_bwd_route(d, add=False, mask=False, y=False):
+    """the kernel vlfb_maxpool_bwd (add / mask given or not) or vlfb_maxpool_relu_bwd (y) runs for this descriptor, as text
+    (vlfb_maxpool_bwd_describe); a host-side query, no GPU needed"""
+    buf = C.create_string_buffer(64)
+    _check(lib().vlfb_maxpool_bwd_describe(C.byref(d), int(bool(add)), int(bool(mask)), int(bool(y)), buf, 64),
+           "vlfb_maxpool_bwd_describe")
+    return buf.value.decode()
 
 
 def ks_array(ks):
