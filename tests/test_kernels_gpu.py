@@ -256,7 +256,19 @@ def test_batched_gemms_of_the_nonlocal_block(dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_row_bias_and_swapped_roles_gives_transposed_conv_output(dtype):
     """g^T = W_g . x^T with a per-row bias: the transposed 1x1x1 conv output the non-local block needs"""
-    M, Cin, Cout = 150, 64, 128
+    # M = 150 is not a multiple of 4 -> scalar-store epilogue path
+    row_bias_transposed_output(dtype, 150)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_row_bias_on_the_vector_epilogue(dtype):
+    """the same product with M = 152 output columns: whole 16-byte stores, i.e. the row bias in the LDS-staged row form of
+    gemm_nt_kernel (its own copy of the epilogue; the shared nt_apply meets a row bias in test_pipe256_gpu.py)"""
+    row_bias_transposed_output(dtype, 152)
+
+
+def row_bias_transposed_output(dtype, M):
+    Cin, Cout = 64, 128
     gen = torch.Generator().manual_seed(7)
     code = hip.dtype_code(dtype)
     x = q(torch.randn(M, Cin, generator=gen), dtype)
@@ -265,7 +277,6 @@ def test_row_bias_and_swapped_roles_gives_transposed_conv_output(dtype):
     O = torch.empty(Cout, M, device=dev(), dtype=dtype)
     desc = hip.conv_desc(mode=hip.FPROP, dtype=code, out_dtype=code, N=1, Tr=1, Hr=1, Wr=Cout,
                          Ts=1, Hs=1, Ws=Cout, Cs=Cin, Cn=M, bias_mode=hip.BIAS_ROW)
-    # M = 150 is not a multiple of 4 -> scalar-store epilogue path
     hip.conv_run(desc, gpu(w, dtype), gpu(x, dtype), None, O, bias=gpu(b))
     ref = (x.double() @ w.double().t() + b.double()).t()
     assert rel_err(O.float(), ref) < TOL[dtype]

@@ -41,6 +41,8 @@ NT_CASES = {
     "spatial3": (2, 64, 256, 2, 23, 23, (1, 3, 3), (1, 1, 1), (0, 1, 1), (1, 1, 1)),
     "spatial3_dil2": (1, 128, 128, 3, 20, 20, (1, 3, 3), (1, 1, 1), (0, 2, 2), (1, 2, 2)),
     "spatial3_s2_fprop_only": (1, 64, 256, 2, 47, 47, (1, 3, 3), (1, 2, 2), (0, 1, 1), (1, 1, 1)),
+    # the shape of ident_w128 with a bias per output ROW (VLFB_BIAS_ROW) instead of per column
+    "ident_w128_rowbias_fprop_only": (1, 192, 128, 4, 16, 17, (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1)),
 }
 
 
@@ -52,7 +54,8 @@ def test_nt_pipe256_is_bit_identical_to_tile128_and_matches_fp64(case):
     x = q(torch.randn(N, Cin, T, H, W, generator=gen), BF)
     w = q(torch.randn(Cout, Cin, *k, generator=gen) / math.sqrt(Cin * k[0] * k[1] * k[2]), BF)
     To, Ho, Wo = [(a + 2 * pp - dd * (kk - 1) - 1) // ss + 1 for a, kk, ss, pp, dd in zip((T, H, W), k, s, p, d)]
-    bias = torch.randn(Cout, generator=gen)
+    row_bias = "rowbias" in case
+    bias = torch.randn(N * To * Ho * Wo if row_bias else Cout, generator=gen)
     res = q(torch.randn(N, Cout, To, Ho, Wo, generator=gen), BF)
     A = to_nthwc(x).to(dev(), BF)
     Bw = w_to_kernel(w).to(dev(), BF)
@@ -64,7 +67,10 @@ def test_nt_pipe256_is_bit_identical_to_tile128_and_matches_fp64(case):
         for rep in range(3 if algo == hip.ALGO_PIPE256 else 1):
             O = torch.full((N, To, Ho, Wo, Cout), float("nan"), device=dev(), dtype=BF)
             desc = hip.conv_desc(mode=hip.FPROP, dtype=hip.BF16, out_dtype=hip.BF16, N=N, Tr=To, Hr=Ho, Wr=Wo, Ts=T, Hs=H,
-                                 Ws=W, Cs=Cin, Cn=Cout, relu=1, bias_mode=hip.BIAS_COL, algo=algo, **_geom(k, s, p, d))
+                                 Ws=W, Cs=Cin, Cn=Cout, relu=1, bias_mode=hip.BIAS_ROW if row_bias else hip.BIAS_COL, algo=algo,
+                                 **_geom(k, s, p, d))
+            if row_bias:
+                assert hip.conv_plan(desc).split()[0] == ("nt8" if algo == hip.ALGO_PIPE256 else "nt"), hip.conv_plan(desc)
             hip.conv_run(desc, A, Bw, None, O, bias=bg, R=R)
             O32 = torch.full((N, To, Ho, Wo, Cout), float("nan"), device=dev(), dtype=torch.float32)
             desc = hip.conv_desc(mode=hip.FPROP, dtype=hip.BF16, out_dtype=hip.F32, N=N, Tr=To, Hr=Ho, Wr=Wo, Ts=T, Hs=H,
@@ -77,6 +83,11 @@ def test_nt_pipe256_is_bit_identical_to_tile128_and_matches_fp64(case):
         assert torch.equal(O.view(torch.int16), ref.view(torch.int16)), "fprop: pipelined kernel differs from the 128x128 kernel"
         assert torch.equal(O32.view(torch.int32), ref32.view(torch.int32)), "fprop fp32-out differs"
     assert rel_err(to_ncthw(ref32), 0.5 * y_lin) < 2e-5
+    if row_bias:
+        # the bf16 output with the row bias against fp64: one bf16 rounding of the result, 2^-9 relative per element at the
+        # most, so the norm ratio stays below 2^-9 plus the fp32 accumulation error (2e-5 above); 2^-8 bounds both
+        y_ref = torch.relu(y_lin + bias.double().view(N, 1, To, Ho, Wo) + res.double())
+        assert rel_err(to_ncthw(ref.float()), y_ref) < 2.0 ** -8
     if case.endswith("fprop_only"):
         return
     # ---- dgrad (unit stride: gathered DGRAD instance; 1x1x1: plain rows) with add + mask epilogue --------

@@ -53,10 +53,8 @@ template <int V> __device__ __forceinline__ void st_f(float* p, const float (&v)
 // the canonical pair of y: hi = fp16(y), lo = fp16(y - hi) -- except where that low term, rounded UP to half an ulp of hi,
 // would make fp16(hi + lo) the even neighbour of an odd hi: there lo is the next fp16 towards zero (2^-24 of y)
 __device__ __forceinline__ void pair_of(float y, unsigned short& hi, unsigned short& lo) {
-  hi = f2h(y);
-  const float fh = h2f(hi);
-  lo = f2h(y - fh);
-  if ((lo & 0x7fffu) != 0 && f2h(fh + h2f(lo)) != hi) lo -= 1;
+  split2_h(y, hi, lo);
+  if ((lo & 0x7fffu) != 0 && f2h(h2f(hi) + h2f(lo)) != hi) lo -= 1;
 }
 
 // values in the format of the tensor: two fp16 planes `n` elements apart (8 channels per lane) or fp32 (4 per lane)

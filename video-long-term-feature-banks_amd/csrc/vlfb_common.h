@@ -154,6 +154,40 @@ template <typename T> struct Vec16x16bit {
 template <> struct Vec16<bf16_t> : Vec16x16bit<bf16_t> {};
 template <> struct Vec16<f16_t> : Vec16x16bit<f16_t> {};
 
+// ---- the three 16-bit forms of an fp32 result ---------------------------------------------
+// (1) The TWO-TERM split, hi = T(v), lo = T(v - hi): with T = f16_t the storage format of the whole "mix" forward (two
+// fp16 planes, value = hi + lo), with either 16-bit T the two-term output of a 16-bit launch (GP::O2).  Every producer of
+// such a pair -- the NT epilogues, the stem, the split-bf16 epilogue, the cast / weight-prep passes, SpatialBN -- goes
+// through split2, so they agree bit for bit (tests/test_pair_gpu.py, test_stem_gpu.py, test_split_gpu.py compare them;
+// test_conv_launches_gpu.py::test_two_plane_epilogue_range_contract pins the range behaviour: a value past the fp16
+// limit comes back non-finite, never as a wrong finite number -- nothing saturates).  The subtraction is __fsub_rn: never
+// contracted with a multiply that produced v.  Words hold two elements, the first in the low half.
+template <typename T>
+__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
+  hi = Elem<T>::pack2(a, b);
+  lo = Elem<T>::pack2(__fsub_rn(a, Elem<T>::lo(hi)), __fsub_rn(b, Elem<T>::hi(hi)));
+}
+template <typename T, int N>
+__device__ __forceinline__ void split2(const float (&v)[N], uint32_t (&hi)[N / 2], uint32_t (&lo)[N / 2]) {
+#pragma unroll
+  for (int i = 0; i < N / 2; ++i) split2<T>(v[2 * i], v[2 * i + 1], hi[i], lo[i]);
+}
+// (one fp16 element)
+__device__ __forceinline__ void split2_h(float v, unsigned short& hi, unsigned short& lo) {
+  uint32_t h, l;
+  split2<f16_t>(v, 0.f, h, l);
+  hi = (unsigned short)(h & 0xffffu); lo = (unsigned short)(l & 0xffffu);
+}
+// (2) The fp16 COPY of four fp32 outputs of a two-plane launch (read by the fp16 backward as operand and as ReLU mask:
+// positives stay positive, f2h_pos), and (3) the copy of four fp32 outputs of a plain 16-bit launch, rounded to T.
+__device__ __forceinline__ uint2 copy4_h_pos(const float (&v)[4]) {
+  return make_uint2(pack_h2_pos(v[0], v[1]), pack_h2_pos(v[2], v[3]));
+}
+template <typename T>
+__device__ __forceinline__ uint2 copy4(const float (&v)[4]) {
+  return make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3]));
+}
+
 // vlfb_ops.hip: column sums without atomics -- per-slab partial rows that the caller folds in a fixed order
 int colsum_slabs(int dtype, long long rows, long long cols);
 int colsum_partials(const void* g, int dtype, long long rows, long long cols, long long ld, float* partials, hipStream_t s);

@@ -154,7 +154,10 @@ __global__ __launch_bounds__(512) void conv_rows64_kernel(const GP p, const int 
         __builtin_amdgcn_sched_barrier(0);
       }
 
-      // ---- epilogue in registers: lane = position m*16 + l15 of row h, channels wq*32 + g*8 .. +7 -----------------
+      // ---- epilogue in registers: lane = position m*16 + l15 of row h, channels wq*32 + g*8 .. +7 (the steps of nt_apply,
+      // vlfb_gemm_common.h, in this kernel's own text: through the shared function six of the eight instances took 1-8 more
+      // VGPRs, e.g. 184 -> 190 and 180 -> 188; spelled as there -- __fmul_rn, then __fadd_rn per step -- except that no row bias
+      // and no low residual term reach this kernel)
       if (h < nrow) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {

@@ -405,6 +405,87 @@ __device__ __forceinline__ void load_elems_epi(bool nt, const T* p, float (&v)[N
   else load_elems<T, N>(p, v);
 }
 
+// ---- the output epilogues -------------------------------------------------------------------------------------------
+// NT (FPROP / DGRAD).  The order is fixed:  v = alpha * acc;  + bias;  + R;  + R_lo;  ReLU;  mask;  store O;  then O_lo
+// (split2, vlfb_common.h) or a 16-bit copy of an fp32 O (copy4_h_pos / copy4).  Every step rounds to fp32 on its own (__fmul_rn / __fadd_rn: no caller's
+// multiply is ever contracted into an addition), so a launch gives the same bits whichever kernel family the planner
+// resolves it to -- which the tests demand: test_pipe256_gpu.py (nt8 against nt), test_stream_gpu.py (nts),
+// test_stem_gpu.py, test_pair_gpu.py, test_dgrad_s2_gpu.py, test_conv_launches_gpu.py.  A kernel keeps what is its own:
+// where the scaled values come from (the LDS-staged tile, or __fmul_rn(acc, alpha) in registers), where the residual and
+// mask rows come from (registers filled before the k-loop, or load_elems_epi), and its store instruction.
+// Callers: gemm_nt8_kernel and both stem kernels (which have no row operands: NoRows).  gemm_nt_kernel, gemm_nts_kernel
+// and conv_rows64_kernel spell the same steps out in their own text, because some of their instances took more VGPRs
+// through this function (figures at each copy and in profiles/epilogue_dedup_resources.txt): a change to the order or
+// the rounding is made HERE and in those three.  The stores stay with each kernel; what they share is split2 / copy4*.
+//
+// nt_apply: everything between the scaling and the store, on EPT consecutive columns of output row m.  bcol: the EPT
+// column biases (read under VLFB_BIAS_COL only).  res / res_lo / mask: callables  bool(float (&r)[EPT])  that fetch this
+// lane's residual, low residual term and mask values, or return false when the launch has no such operand.
+// (column biases staged in LDS on a 16-byte boundary: nt_apply then reads them with 16-byte accesses)
+__device__ __forceinline__ const float* aligned16(const void* p) { return static_cast<const float*>(__builtin_assume_aligned(p, 16)); }
+struct NoRows {
+  template <int N> __device__ __forceinline__ bool operator()(float (&)[N]) const { return false; }
+};
+template <int EPT, typename Res, typename ResLo, typename Msk>
+__device__ __forceinline__ void nt_apply(const GP& p, float (&v)[EPT], const float* bcol, int m, Res&& res, ResLo&& res_lo, Msk&& mask) {
+  if (p.bias_mode == VLFB_BIAS_COL) {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) v[e] = __fadd_rn(v[e], bcol[e]);
+  } else if (p.bias_mode == VLFB_BIAS_ROW) {
+    const float b = p.bias[m];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) v[e] = __fadd_rn(v[e], b);
+  }
+  float r[EPT];
+  if (res(r)) {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) v[e] = __fadd_rn(v[e], r[e]);
+  }
+  if (res_lo(r)) {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) v[e] = __fadd_rn(v[e], r[e]);
+  }
+  if (p.relu) {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) v[e] = fmaxf(v[e], 0.f);
+  }
+  if (mask(r)) {
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) v[e] = r[e] > 0.f ? v[e] : 0.f;
+  }
+}
+
+// TN (WGRAD): a lane holds 4 consecutive columns qb .. qb + 3 of output row pp per accumulator fragment.  With splits > 1
+// the raw sums go to this split's slab of the workspace (the reduce pass scales them); otherwise
+// O = alpha * rowscale[pp] * acc (+ O with GP::accumulate).  Callers: gemm_tn_kernel, gemm_tn_sp_kernel, gemm_tn8_kernel
+// (gemm_tn_tr_kernel keeps its own text: one instance took 3 more VGPRs).  tests: test_kernels_gpu.py::test_wgrad_with_bias_gradient,
+// test_wgrad_rows_gpu.py, test_split_gpu.py, test_pipe256_gpu.py.
+__device__ __forceinline__ float tn_row_scale(const GP& p, int pp) {
+  return (p.splits > 1 || !p.rowscale) ? 1.f : p.rowscale[pp];
+}
+template <typename OutT>
+__device__ __forceinline__ void tn_store(const GP& p, const f32x4_v& acc, int z, int split, int pp, int qb, float rs) {
+  if (qb >= p.K) return;
+  const bool vec_ok = (p.ldo & 3) == 0;
+  const int cnt = (p.K - qb) < 4 ? (p.K - qb) : 4;
+  const long long idx = (long long)pp * p.ldo + qb;
+  float v[4];
+  if (p.splits > 1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = acc[r];
+    store4<float>(reinterpret_cast<char*>(p.ws), (long long)split * ((long long)p.Ncols * p.ldo) + idx, v, cnt, vec_ok);
+  } else {
+    char* Ob = p.O + (long long)z * p.o_bs * (long long)sizeof(OutT);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float x = acc[r] * p.alpha * rs;
+      if (p.accumulate && r < cnt) x += ld_elem<OutT>(Ob, idx + r);
+      v[r] = x;
+    }
+    store4<OutT>(Ob, idx, v, cnt, vec_ok);
+  }
+}
+
 // XCD-aware remap of a linear workgroup id: consecutive ids on one XCD share operand panels.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int nx = 8;

@@ -442,6 +442,11 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
     // result is written with full 16-byte accesses, whole rows of the tile per wavefront.
     // The tile is staged in one pass when it fits the LDS of this launch, else in two halves
     // (rows of wave-row 0, then of wave-row 1): p.epi is 1 or 2.
+    // The arithmetic is that of nt_apply (vlfb_gemm_common.h: order and rounding are defined there) in this kernel's own
+    // text: through that function and a shared row store 33 of its instances took 1-4 more VGPRs, and the thin-K DGRAD
+    // instances (PRE, BN = 64: 79 -> 81, 80 -> 84) and the two-plane plain-row PRE instance (128 -> 130) lost a wave per SIMD.
+    // (The additions below are written `+=` where nt_apply writes __fadd_rn: the same bits, because v comes out of LDS and
+    // no multiply stands next to any of them.  Keep it so: a product formed here must go through __fmul_rn first.)
     constexpr int CPR = BN / 4;          // 16-byte fp32 chunks per tile row
     const int epi = p.epi;
     auto stage = [&](int h) {
@@ -536,16 +541,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
                              make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2 % EPT], v[3 % EPT])));
           }
         } else {
-          const uint4 hv = make_uint4(Elem<OutT>::pack2(v[0], v[1]), Elem<OutT>::pack2(v[2 % EPT], v[3 % EPT]),
-                                      Elem<OutT>::pack2(v[4 % EPT], v[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT], v[7 % EPT]));
           if constexpr (POOL2) {
             static_assert(!POOL2 || (NPASS == 4 && RPP == 32), "POOL2: passes gp and gp + 2 are rows r and r + 64");
             // the two planes this row WOULD have stored; the window maximum is taken on their sum hi + lo with a strict >
             // in tap order from -inf, exactly as maxpool_fwd_pair_kernel does on the stored planes (never on v itself)
-            float h[EPT];
-            unpack_elems<OutT, EPT>(hv, h);
-            const uint4 lv = make_uint4(Elem<OutT>::pack2(v[0] - h[0], v[1] - h[1]), Elem<OutT>::pack2(v[2 % EPT] - h[2 % EPT], v[3 % EPT] - h[3 % EPT]),
-                                        Elem<OutT>::pack2(v[4 % EPT] - h[4 % EPT], v[5 % EPT] - h[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT] - h[6 % EPT], v[7 % EPT] - h[7 % EPT]));
+            uint32_t hw[EPT / 2], lw[EPT / 2];
+            split2<OutT>(v, hw, lw);
+            const uint4 hv = make_uint4(hw[0], hw[1], hw[2 % (EPT / 2)], hw[3 % (EPT / 2)]);
+            const uint4 lv = make_uint4(lw[0], lw[1], lw[2 % (EPT / 2)], lw[3 % (EPT / 2)]);
             const int srow = row & (BM / 2 - 1);                     // the LDS row of tap 0 of this lane's window
             uint4* const keep_h = reinterpret_cast<uint4*>(smem + ((srow * CPR + ((tc * (EPT / 4)) ^ (srow & 7))) << 4));
             uint4* const keep_l = reinterpret_cast<uint4*>(smem + ((srow * CPR + ((tc * (EPT / 4) + 1) ^ (srow & 7))) << 4));
@@ -577,13 +580,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
               if (p.AM) st8_epi(nt, p.AM + prow * p.Ncols + ncol, make_uint2(am[0], am[1]));
             }
           } else {
-          st16_epi(nt, o, hv);
+          // the plain 16-bit store every launch makes; split2 runs only where there is a plane for the low term (its hi words
+          // are these same packs again, which the compiler merges)
+          st16_epi(nt, o, make_uint4(Elem<OutT>::pack2(v[0], v[1]), Elem<OutT>::pack2(v[2 % EPT], v[3 % EPT]),
+                                     Elem<OutT>::pack2(v[4 % EPT], v[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT], v[7 % EPT])));
           if (O2b) {                                 // low term: what the rounding of the stored value lost
-            float h[EPT];
-            unpack_elems<OutT, EPT>(hv, h);
-            st16_epi(nt, reinterpret_cast<OutT*>(O2b) + mpos * p.ldo + ncol,
-                     make_uint4(Elem<OutT>::pack2(v[0] - h[0], v[1] - h[1]), Elem<OutT>::pack2(v[2 % EPT] - h[2 % EPT], v[3 % EPT] - h[3 % EPT]),
-                                Elem<OutT>::pack2(v[4 % EPT] - h[4 % EPT], v[5 % EPT] - h[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT] - h[6 % EPT], v[7 % EPT] - h[7 % EPT])));
+            uint32_t hw[EPT / 2], lw[EPT / 2];
+            split2<OutT>(v, hw, lw);
+            st16_epi(nt, reinterpret_cast<OutT*>(O2b) + mpos * p.ldo + ncol, make_uint4(lw[0], lw[1], lw[2 % (EPT / 2)], lw[3 % (EPT / 2)]));
           }
           }
         }

@@ -320,60 +320,27 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const GP p) {
           const float4 t = *reinterpret_cast<const float4*>(smem + ((sr * CPR + (c ^ (sr & 7))) << 4));
           v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
         }
-        if (p.bias_mode == VLFB_BIAS_COL) {
-#pragma unroll
-          for (int e = 0; e < EPT; ++e) v[e] += p.bias[ncol + e];
-        } else if (p.bias_mode == VLFB_BIAS_ROW) {
-          const float b = p.bias[m];
-#pragma unroll
-          for (int e = 0; e < EPT; ++e) v[e] += b;
-        }
         const long long ridx = (long long)m * p.ldr + ncol;
-        if (Rb) {
-          float r[EPT];
-          load_elems_epi<T, EPT>(nt, reinterpret_cast<const T*>(Rb) + ridx, r);
-#pragma unroll
-          for (int e = 0; e < EPT; ++e) v[e] += r[e];
-        }
-        if constexpr (sizeof(OutT) == 2) {
-          if (R2b) {
-            float r[EPT];
-            load_elems_epi<T, EPT>(nt, reinterpret_cast<const T*>(R2b) + ridx, r);
-#pragma unroll
-            for (int e = 0; e < EPT; ++e) v[e] += r[e];
-          }
-        }
-        if (p.relu) {
-#pragma unroll
-          for (int e = 0; e < EPT; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if (Mb) {
-          float r[EPT];
-          load_elems_epi<T, EPT>(nt, reinterpret_cast<const T*>(Mb) + ridx, r);
-#pragma unroll
-          for (int e = 0; e < EPT; ++e) v[e] = r[e] > 0.f ? v[e] : 0.f;
-        }
-        OutT* o = reinterpret_cast<OutT*>(Ob) + (long long)m * p.ldo + ncol;
-        if (sizeof(OutT) == 4) {
+        auto rows_of = [&](const char* base) {                            // a row operand of this lane, read here
+          return [=](float (&r)[EPT]) {
+            if (!base) return false;
+            load_elems_epi<T, EPT>(nt, reinterpret_cast<const T*>(base) + ridx, r);
+            return true;
+          };
+        };
+        nt_apply<EPT>(p, v, p.bias ? p.bias + ncol : nullptr, m, rows_of(Rb), rows_of(sizeof(OutT) == 2 ? R2b : nullptr), rows_of(Mb));
+        // store: O, then (16-bit O) its low term, or (fp32 O) the 16-bit copy -- fp16 with positives kept on a two-plane
+        // launch, else the operand type.  O2b may be null.
+        const long long oidx = (long long)m * p.ldo + ncol;
+        OutT* o = reinterpret_cast<OutT*>(Ob) + oidx;
+        if constexpr (sizeof(OutT) == 4) {
           st16_epi(nt, o, make_float4(v[0], v[1], v[2], v[3]));
-          if constexpr (PAIR) {       // O2 = the fp16 copy of an fp32 output (vlfb_gemm_nt.h)
-            if (O2b) st8_epi(nt, reinterpret_cast<unsigned short*>(O2b) + (long long)m * p.ldo + ncol,
-                             make_uint2(pack_h2_pos(v[0], v[1]), pack_h2_pos(v[2 % EPT], v[3 % EPT])));
-          } else {                    // ... of a 16-bit launch: the same values rounded to T
-            if (O2b) st8_epi(nt, reinterpret_cast<T*>(O2b) + (long long)m * p.ldo + ncol,
-                             make_uint2(Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2 % EPT], v[3 % EPT])));
-          }
+          if (O2b) st8_epi(nt, reinterpret_cast<unsigned short*>(O2b) + oidx, PAIR ? copy4_h_pos(v) : copy4<T>(v));
         } else {
-          const uint4 hv = make_uint4(Elem<OutT>::pack2(v[0], v[1]), Elem<OutT>::pack2(v[2 % EPT], v[3 % EPT]),
-                                      Elem<OutT>::pack2(v[4 % EPT], v[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT], v[7 % EPT]));
-          st16_epi(nt, o, hv);
-          if (O2b) {
-            float h[EPT];
-            unpack_elems<OutT, EPT>(hv, h);
-            st16_epi(nt, reinterpret_cast<OutT*>(O2b) + (long long)m * p.ldo + ncol,
-                     make_uint4(Elem<OutT>::pack2(v[0] - h[0], v[1] - h[1]), Elem<OutT>::pack2(v[2 % EPT] - h[2 % EPT], v[3 % EPT] - h[3 % EPT]),
-                                Elem<OutT>::pack2(v[4 % EPT] - h[4 % EPT], v[5 % EPT] - h[5 % EPT]), Elem<OutT>::pack2(v[6 % EPT] - h[6 % EPT], v[7 % EPT] - h[7 % EPT])));
-          }
+          uint32_t hi[EPT / 2], lo[EPT / 2];
+          split2<OutT>(v, hi, lo);
+          st16_epi(nt, o, make_uint4(hi[0], hi[1], hi[2], hi[3]));
+          if (O2b) st16_epi(nt, reinterpret_cast<OutT*>(O2b) + oidx, make_uint4(lo[0], lo[1], lo[2], lo[3]));
         }
       }
     }

@@ -248,7 +248,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_nts_kernel(const GP p, const int
 #pragma unroll
           for (int u = 0; u < UK; ++u) { cur[f][u][0] = nxt[f][u][0]; cur[f][u][1] = nxt[f][u][1]; }
       }
-      // ---- epilogue in registers: lane = position l15, channels q*32 + g*8 .. +7 -----------------------
+      // ---- epilogue in registers: lane = position l15, channels q*32 + g*8 .. +7 (the steps of nt_apply, vlfb_gemm_common.h,
+      // in this kernel's own text: through the shared function the <bf16, 4, 1, 3, true, 16> instance went from 106 to 110 VGPRs;
+      // spelled as there -- __fmul_rn, then __fadd_rn per step -- except that no row bias and no low residual term reach this kernel)
 #pragma unroll
       for (int f = 0; f < MF; ++f) {
         const int m = blk * RB + f * 16 + l15;

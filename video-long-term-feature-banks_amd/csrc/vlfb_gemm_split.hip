@@ -170,10 +170,10 @@ __device__ __forceinline__ void nt_epilogue(const GP& p, const f32x4_v (&acc)[FN
       v[2] = mv[gp].z > 0.f ? v[2] : 0.f; v[3] = mv[gp].w > 0.f ? v[3] : 0.f;
       const long long oidx = mo * p.ldo + ncol;
       if (pair) {
-        const unsigned short h0 = f2h(v[0]), h1 = f2h(v[1]), h2 = f2h(v[2]), h3 = f2h(v[3]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(Ob) + oidx) = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16));
-        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.O2 + (long long)z * p.o_bs * 2) + oidx) =
-            make_uint2((uint32_t)f2h(v[0] - h2f(h0)) | ((uint32_t)f2h(v[1] - h2f(h1)) << 16), (uint32_t)f2h(v[2] - h2f(h2)) | ((uint32_t)f2h(v[3] - h2f(h3)) << 16));
+        uint32_t hi[2], lo[2];
+        split2<f16_t>(v, hi, lo);
+        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(Ob) + oidx) = make_uint2(hi[0], hi[1]);
+        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.O2 + (long long)z * p.o_bs * 2) + oidx) = make_uint2(lo[0], lo[1]);
         continue;
       }
       st16_epi(p.nt_epi != 0, reinterpret_cast<float*>(Ob) + oidx, make_float4(v[0], v[1], v[2], v[3]));      // (GP::nt_epi)
@@ -812,36 +812,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_sp_kernel(const GP p) {
     __syncthreads();
   }
 
-  // ---- epilogue (as gemm_tn_kernel): lane holds qq = qb + 0..3 for output row pp ----
-  const bool vec_ok = (p.ldo & 3) == 0;
-  const bool to_ws = p.splits > 1;
+  // ---- epilogue: lane holds qq = qb + 0..3 for output row pp ----
 #pragma unroll
   for (int i = 0; i < FP; ++i) {
     const int pp = p0 + wp * WP + i * 16 + l15;
     if (pp >= p.Ncols) continue;
-    const float rs = (to_ws || !p.rowscale) ? 1.f : p.rowscale[pp];
+    const float rs = tn_row_scale(p, pp);
 #pragma unroll
-    for (int j = 0; j < FQ; ++j) {
-      const int qb = q0 + wq * WQ + j * 16 + g * 4;
-      if (qb >= p.K) continue;
-      const int cnt = (p.K - qb) < 4 ? (p.K - qb) : 4;
-      const long long idx = (long long)pp * p.ldo + qb;
-      float v[4];
-      if (to_ws) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[j][i][r];
-        store4<float>(reinterpret_cast<char*>(p.ws), (long long)split * ((long long)p.Ncols * p.ldo) + idx, v, cnt, vec_ok);
-      } else {
-        char* Ob = p.O + (long long)z * p.o_bs * 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float x = acc[j][i][r] * p.alpha * rs;
-          if (p.accumulate && r < cnt) x += ld_elem<float>(Ob, idx + r);
-          v[r] = x;
-        }
-        store4<float>(Ob, idx, v, cnt, vec_ok);
-      }
-    }
+    for (int j = 0; j < FQ; ++j) tn_store<float>(p, acc[j][i], z, split, pp, q0 + wq * WQ + j * 16 + g * 4, rs);
   }
 }
 

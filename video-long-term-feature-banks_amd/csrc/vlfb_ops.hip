@@ -141,10 +141,7 @@ __device__ __forceinline__ void store_terms(bf16_t* dst, long long idx, long lon
 // the two fp16 terms of v * VLFB_MIX_W2_SCALE, `stride` elements apart: h = fp16(sv), l = fp16(sv - h).  The scale keeps
 // the low term of a small weight in the fp16 normal range; the launch's alpha carries its inverse.
 __device__ __forceinline__ void store_scaled2(unsigned short* o, long long stride, float v) {
-  const float sv = v * VLFB_MIX_W2_SCALE;
-  const unsigned short h = f2h(sv);
-  o[0] = h;
-  o[stride] = f2h(sv - h2f(h));
+  split2_h(v * VLFB_MIX_W2_SCALE, o[0], o[stride]);
 }
 
 // ---- weight operand formats -------------------------------------------------------------------
@@ -509,11 +506,11 @@ static bool stream_nt() {
 __global__ void pair_split_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, long long n, bool nt) {
   for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * blockDim.x * 4) {
     const uint4 u = stream_ld16(nt, src + i);
-    const float4 v = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
-    const unsigned short h0 = f2h(v.x), h1 = f2h(v.y), h2 = f2h(v.z), h3 = f2h(v.w);
-    stream_st8(nt, dst + i, make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16)));
-    stream_st8(nt, dst + n + i, make_uint2((uint32_t)f2h(v.x - h2f(h0)) | ((uint32_t)f2h(v.y - h2f(h1)) << 16),
-                                           (uint32_t)f2h(v.z - h2f(h2)) | ((uint32_t)f2h(v.w - h2f(h3)) << 16)));
+    const float v[4] = {__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
+    uint32_t hi[2], lo[2];
+    split2<f16_t>(v, hi, lo);
+    stream_st8(nt, dst + i, make_uint2(hi[0], hi[1]));
+    stream_st8(nt, dst + n + i, make_uint2(lo[0], lo[1]));
   }
 }
 __global__ void pair_join_kernel(const unsigned short* __restrict__ src, float* __restrict__ dst, long long n, bool nt) {

@@ -180,19 +180,8 @@ __global__ __launch_bounds__(512) void stem_fprop_kernel(const GP p, const int h
             for (int e = 0; e < 2; ++e)
 #pragma unroll
               for (int r = 0; r < 4; ++r) v[e * 4 + r] = __fmul_rn(acc[m][2 * q + e][r], p.alpha);
-            if (p.bias_mode == VLFB_BIAS_COL) {
-              const float4 b0 = *reinterpret_cast<const float4*>(bias_l + q * 32 + g * 8);
-              const float4 b1 = *reinterpret_cast<const float4*>(bias_l + q * 32 + g * 8 + 4);
-              v[0] = __fadd_rn(v[0], b0.x); v[1] = __fadd_rn(v[1], b0.y); v[2] = __fadd_rn(v[2], b0.z); v[3] = __fadd_rn(v[3], b0.w);
-              v[4] = __fadd_rn(v[4], b1.x); v[5] = __fadd_rn(v[5], b1.y); v[6] = __fadd_rn(v[6], b1.z); v[7] = __fadd_rn(v[7], b1.w);
-            }
-            if (p.relu) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            u32x4_s o;
-            o.x = Elem<T>::pack2(v[0], v[1]); o.y = Elem<T>::pack2(v[2], v[3]);
-            o.z = Elem<T>::pack2(v[4], v[5]); o.w = Elem<T>::pack2(v[6], v[7]);
+            nt_apply<8>(p, v, aligned16(bias_l + q * 32 + g * 8), row0 + m * 16 + l15, NoRows{}, NoRows{}, NoRows{});
+            const u32x4_s o = {Elem<T>::pack2(v[0], v[1]), Elem<T>::pack2(v[2], v[3]), Elem<T>::pack2(v[4], v[5]), Elem<T>::pack2(v[6], v[7])};
             __builtin_amdgcn_raw_buffer_store_b128(o, rsO, (int)(oo + q * 64u), 0, 0);
           }
         }
@@ -335,26 +324,10 @@ __global__ __launch_bounds__(512) void stem_fprop_pair_kernel(const GP p, const 
             for (int e = 0; e < 2; ++e)
 #pragma unroll
               for (int r = 0; r < 4; ++r) v[e * 4 + r] = __fmul_rn(acc[m][2 * q + e][r], p.alpha);
-            if (p.bias_mode == VLFB_BIAS_COL) {
-              const float4 b0 = *reinterpret_cast<const float4*>(bias_l + q * 32 + g * 8);
-              const float4 b1 = *reinterpret_cast<const float4*>(bias_l + q * 32 + g * 8 + 4);
-              v[0] = __fadd_rn(v[0], b0.x); v[1] = __fadd_rn(v[1], b0.y); v[2] = __fadd_rn(v[2], b0.z); v[3] = __fadd_rn(v[3], b0.w);
-              v[4] = __fadd_rn(v[4], b1.x); v[5] = __fadd_rn(v[5], b1.y); v[6] = __fadd_rn(v[6], b1.z); v[7] = __fadd_rn(v[7], b1.w);
-            }
-            if (p.relu) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            u32x4_s o, ol;
-            uint32_t w4[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w4[e] = Elem<f16_t>::pack2(v[2 * e], v[2 * e + 1]);
-            o.x = w4[0]; o.y = w4[1]; o.z = w4[2]; o.w = w4[3];
-            uint32_t l4[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              l4[e] = Elem<f16_t>::pack2(__fsub_rn(v[2 * e], Elem<f16_t>::lo(w4[e])), __fsub_rn(v[2 * e + 1], Elem<f16_t>::hi(w4[e])));
-            ol.x = l4[0]; ol.y = l4[1]; ol.z = l4[2]; ol.w = l4[3];
+            nt_apply<8>(p, v, aligned16(bias_l + q * 32 + g * 8), row0 + m * 16 + l15, NoRows{}, NoRows{}, NoRows{});
+            uint32_t w4[4], l4[4];
+            split2<f16_t>(v, w4, l4);
+            const u32x4_s o = {w4[0], w4[1], w4[2], w4[3]}, ol = {l4[0], l4[1], l4[2], l4[3]};
             if (p.nt_epi) {            // (aux = 2: the non-temporal hint, GP::nt_epi)
               __builtin_amdgcn_raw_buffer_store_b128(o, rsO, (int)(oo + q * 64u), 0, 2);
               __builtin_amdgcn_raw_buffer_store_b128(ol, rsO2, (int)(oo + q * 64u), 0, 2);
