@@ -1,5 +1,5 @@
 """Case table, generators and references shared by tests/test_pool_cases_host.py and tests/test_pool_gpu.py (the pooling
-kernels of csrc/vlfb_ops.hip: vlfb_maxpool_fwd / _bwd / _relu_bwd, vlfb_avgpool_fwd / _bwd / _bwd_two_term).  CPU only;
+kernels of csrc/vlfb_pool.hip: vlfb_maxpool_fwd / _bwd / _relu_bwd, vlfb_avgpool_fwd / _bwd / _bwd_two_term).  CPU only;
 imports no vlfb.  Written from the contract of include/vlfb.h, not from the kernels.  Tensors are channels-last
 (N, T, H, W, C) throughout.
 
@@ -21,6 +21,12 @@ Average pools are compared per element with the fp64 reference under
   largest n here, 392).  A 16-bit output rounds once more (the ulp term; dropped for fp32 outputs).  Forward: the terms are
   x / window, n = window (2 * window for hi + lo planes).  Backward: the terms are dy / window per covering window, plus
   `add`; n = covering windows (+ 1 with add).
+The average FORWARD pools are, beyond that bound, compared BIT FOR BIT with an fp32 emulation of their order of operations (no
+multiply inside the sum, so nothing depends on fused multiply-adds):
+  windowed  per output element, in fp32: start at +0; add the taps ascending in (a, b, c) -- of two planes fl32(hi + lo), formed
+            before it is added; multiply once by fl32(1 / window); round once to the output type (fp32 for two planes).
+  global    (one window = the whole clip) the positions in (t, h, w) order are rows 0 .. rows - 1: each of 32 row lanes sums
+            rows rl, rl + 32, ... from +0, then the 32 partial sums are added in lane order from +0; multiply and round as above.
 """
 import collections
 import functools
@@ -273,6 +279,30 @@ def avg_fwd(x, case, lo=None):
         sabs = sabs + w.abs() + (wl.abs() if lo is not None else 0)
     n = window * (2 if lo is not None else 1)
     return mean / window, (n + 1) * U32 * sabs / window
+
+
+def avg_fwd_emulated(x, case, lo=None):
+    """the fp32-ordered emulation of the module docstring: sequential fp32 tensor adds.  x in any float type -> that type; with
+    `lo`, the two fp16 planes -> fp32"""
+    window = case.k[0] * case.k[1] * case.k[2]
+    geo = MaxCase(case.name, case.k, case.s, (0, 0, 0), case.shape, case.C, None, None)
+    v = x.float() if lo is None else x.float() + lo.float()
+    if case.is_global:
+        N, C = v.shape[0], v.shape[4]
+        rows = v.reshape(N, -1, C)
+        lanes = torch.zeros((N, 32, C), dtype=torch.float32)
+        for r in range(rows.shape[1]):
+            lanes[:, r % 32] += rows[:, r]
+        acc = torch.zeros((N, C), dtype=torch.float32)
+        for j in range(32):
+            acc = acc + lanes[:, j]
+        acc = acc.reshape(N, 1, 1, 1, C)
+    else:
+        acc = torch.zeros((v.shape[0],) + out_dims(geo) + (v.shape[4],), dtype=torch.float32)
+        for _, w in _window_views(v, geo, 0.0):                           # (taps in ascending (a, b, c) order)
+            acc = acc + w
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(window), dtype=torch.float32)
+    return (acc * inv).to(x.dtype if lo is None else torch.float32)
 
 
 def avg_bwd(case, dy, add=None, mask=None):

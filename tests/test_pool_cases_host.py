@@ -99,6 +99,11 @@ def test_avg_reference_equals_torch_in_fp64():
         y_ref = F.avg_pool3d(xd, case.k, case.s)
         mean, bound = pc.avg_fwd(x, case)
         assert (nthwc(y_ref.detach()) - mean).abs().max() < 1e-14 and (bound > 0).all()
+        # the fp32-ordered emulation the GPU test compares bit for bit lies inside the bound, plain and on hi + lo planes
+        hi, lo = pc.pair_split(x.float())
+        for emu, (ref, bound) in ((pc.avg_fwd_emulated(x.float(), case), pc.avg_fwd(x.float(), case)),
+                                  (pc.avg_fwd_emulated(hi, case, lo=lo), pc.avg_fwd(hi, case, lo=lo))):
+            assert emu.dtype == torch.float32 and ((emu.double() - ref).abs() <= bound).all(), case.name
         dy = torch.randn(mean.shape, generator=g, dtype=torch.float64)
         (gx,) = torch.autograd.grad(y_ref, (xd,), ncthw(dy))
         dx, _ = pc.avg_bwd(case, dy)

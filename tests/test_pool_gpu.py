@@ -1,11 +1,12 @@
-"""The pooling kernels of csrc/vlfb_ops.hip against the references of tests/pool_cases.py, on the case table that
+"""The pooling kernels of csrc/vlfb_pool.hip against the references of tests/pool_cases.py, on the case table that
 tests/test_pool_cases_host.py holds to its routes and tie conditions.
 
 Max pools are compared bit for bit -- forward values and arg-max taps, and the backward against the fp32-ordered emulation on
 every route (band R=3 / R=2, the three compiled windows with and without the pooled-value mask, the generic kernel with a one-
 and a two-byte arg-max), generator and operand combination.  Average pools are compared per element with the fp64 reference
 under the bound derived in pool_cases; where every input position lies in one window the backward is one product and is
-compared bit for bit, the two-term form included."""
+compared bit for bit, the two-term form included; the average forward pools are also compared bit for bit with the fp32-ordered
+emulation of pool_cases."""
 import ctypes as C
 
 import pytest
@@ -211,6 +212,7 @@ def test_avgpool_forward_within_the_derived_bound(case, dtype_name):
         hip.call("vlfb_pair_split", hip.ptr(V), hip.ptr(P), V.numel())
         planes = P.cpu().view((2,) + shape)
         ref, bound = pc.avg_fwd(planes[0], case, lo=planes[1])
+        emu = pc.avg_fwd_emulated(planes[0], case, lo=planes[1])
         Y = torch.full(ref.shape, float("nan"), device=dev(), dtype=torch.float32)
         hip.call("vlfb_avgpool_fwd", C.byref(d), hip.ptr(P), hip.ptr(Y))
     else:
@@ -218,6 +220,7 @@ def test_avgpool_forward_within_the_derived_bound(case, dtype_name):
         d, od = avg_desc(case, code_of(dtype_name))
         x = torch.randn(shape, generator=g).to(dtype)
         ref, bound = pc.avg_fwd(x, case)
+        emu = pc.avg_fwd_emulated(x, case)
         if dtype_name != "fp32":
             bound = bound + 0.5 * pc.ulp(ref, dtype_name)
         X = gpu(x)
@@ -226,6 +229,7 @@ def test_avgpool_forward_within_the_derived_bound(case, dtype_name):
     assert tuple(ref.shape[1:4]) == od
     print("avgpool_fwd %s %s (%s): worst %.3f of the bound" % (case.name, dtype_name, "global" if case.is_global else "window",
                                                               worst_ratio(Y, ref, bound)))
+    assert same_bits(Y, emu), "%d elements differ from the fp32-ordered emulation" % int((pc.bits(Y.cpu()) != pc.bits(emu)).sum())
 
 
 @pytest.mark.parametrize("dtype_name", list(pc.DTYPES))

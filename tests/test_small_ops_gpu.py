@@ -1,6 +1,6 @@
 """Kernel-level tests of the small operators between the convolution families and the model: every entry point of
 include/vlfb.h that the model tests reach only through vlfb.engine at one shape, and every dispatch branch of
-csrc/vlfb_ops.hip / csrc/vlfb_head.hip that only other shapes select.
+csrc/vlfb_ops.hip / csrc/vlfb_pool.hip / csrc/vlfb_head.hip that only other shapes select.
 
 Calls go through libvlfb_hip.so (ctypes).  Inputs are rounded through the storage type first; every reference is plain
 torch-CPU in fp64 or a bit-exact restatement, none calls the library.  Bit-identity checks between two entry points of the

@@ -544,7 +544,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_kernel(const GP p) {
           if constexpr (POOL2) {
             static_assert(!POOL2 || (NPASS == 4 && RPP == 32), "POOL2: passes gp and gp + 2 are rows r and r + 64");
             // the two planes this row WOULD have stored; the window maximum is taken on their sum hi + lo with a strict >
-            // in tap order from -inf, exactly as maxpool_fwd_pair_kernel does on the stored planes (never on v itself)
+            // in tap order from -inf, exactly as maxpool_fwd_kernel<PairSrc> does on the stored planes (never on v itself).
+            // (The arg-max bytes are the one-byte format that ArgMax in vlfb_pool.hip defines; written here on packed words.)
             uint32_t hw[EPT / 2], lw[EPT / 2];
             split2<OutT>(v, hw, lw);
             const uint4 hv = make_uint4(hw[0], hw[1], hw[2 % (EPT / 2)], hw[3 % (EPT / 2)]);
