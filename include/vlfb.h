@@ -695,6 +695,25 @@ int vlfb_lfb_pack_offsets(const vlfb_lfb_desc* d, const int32_t* count, int64_t*
  * call as for vlfb_lfb_append, first_row >= 0. */
 int vlfb_lfb_pack(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, const int64_t* offsets,
                   int64_t first_row, int64_t rows, void* out, int out_dtype, int32_t* keys, vlfb_stream_t stream);
+/* Packed import, the inverse of vlfb_lfb_pack: rows [first_row, first_row + rows) of a SOURCE bank's packed order, feats
+ * [rows][dim] of feat_dtype (any of the three types), are placed into this bank without keys.  The source has this bank's
+ * n_videos, n_steps and dim; its capacity is src_capacity; src_count int32 [cells] is its count and src_offsets int64
+ * [cells + 1] what vlfb_lfb_pack_offsets wrote for src_count.  Packed row g lies in the cell c with src_offsets[c] <= g <
+ * src_offsets[c + 1], at local slot s = g - src_offsets[c], and goes to slot count[c] + s.  A row whose slot is >= capacity
+ * is not written and counted in *dropped (optional device int32); rows at or beyond src_offsets[cells] are ignored; where
+ * src_offsets do not belong to src_count (s >= min(src_count[c], src_capacity)) nothing is written.  One workgroup per row,
+ * no atomics but *dropped: the result does not depend on the order workgroups run in.
+ * Ordering contract, per source: vlfb_lfb_unpack READS count and never writes it, so every chunk of one source is placed
+ * against the same base, in any chunking (chunks may begin and end inside a cell); after the source's LAST chunk, on the
+ * same stream, vlfb_lfb_unpack_commit publishes it ONCE: count[c] = min(count[c] + min(src_count[c], src_capacity),
+ * capacity).  The next source's chunks come after that commit.  Unpacking every source this way gives count and occupied
+ * slots bit-identical to vlfb_lfb_append of the same packed chunks with their keys.  Limits as vlfb_lfb_pack: cells <=
+ * VLFB_LFB_PACK_MAX_CELLS, 0 <= rows < 2^20 per call, first_row >= 0. */
+int vlfb_lfb_unpack(const vlfb_lfb_desc* d, void* bank, const int32_t* count, const void* feats, int feat_dtype,
+                    const int32_t* src_count, int src_capacity, const int64_t* src_offsets, int64_t first_row, int64_t rows,
+                    int32_t* dropped, vlfb_stream_t stream);
+int vlfb_lfb_unpack_commit(const vlfb_lfb_desc* d, int32_t* count, const int32_t* src_count, int src_capacity,
+                           vlfb_stream_t stream);
 /* Non-finite rows of a finished bank, counted where the bank lives (an inference pass has no loss to guard it: on the
  * 16-bit paths an activation above the format's range becomes Inf or NaN silently, and such a row poisons every training
  * step that samples it).  An occupied row is slot < min(count[cell], capacity) of a cell.  ADDS into out[0] the number of

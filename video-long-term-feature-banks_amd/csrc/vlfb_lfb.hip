@@ -302,6 +302,45 @@ __global__ void lfb_pack_kernel(BankP b, const char* __restrict__ bank, const in
   }
 }
 
+// ---- packed import: the inverse of lfb_pack_kernel ---------------------------------------------------------------------
+// one workgroup per packed source row g = first_row + blockIdx.x (feats row blockIdx.x): its cell c and local slot s come from
+// the source's offsets by the same uniform binary search, it lands in slot count[c] + s of this bank.  `count` is only read,
+// so every chunk of one source is placed against the same base and no row depends on another workgroup.
+__global__ void lfb_unpack_kernel(BankP b, char* bank, const int32_t* __restrict__ count, const void* feats, int fdt,
+                                  const int32_t* __restrict__ src_count, int src_capacity,
+                                  const int64_t* __restrict__ src_offsets, int64_t first_row, int32_t* dropped) {
+  const int64_t cells = (int64_t)b.n_videos * b.n_steps;
+  const int64_t g = first_row + blockIdx.x;
+  if (g >= src_offsets[cells]) return;
+  int64_t lo = 0, hi = cells;             // src_offsets[lo] <= g < src_offsets[hi]
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (src_offsets[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int64_t slot = g - src_offsets[lo];
+  int n = src_count[lo];
+  n = n < 0 ? 0 : (n > src_capacity ? src_capacity : n);
+  if (slot < 0 || slot >= n) return;      // `src_offsets` does not belong to `src_count`: write nothing
+  const int64_t dst = (int64_t)count[lo] + slot;
+  if (dst < 0) return;                    // (a negative count: not a bank's)
+  if (dst >= b.capacity) {
+    if (threadIdx.x == 0 && dropped) atomicAdd(dropped, 1);
+    return;
+  }
+  row_copy(bank, b.dtype, (lo * b.capacity + dst) * (long long)b.dim, feats, fdt, (long long)blockIdx.x * b.dim, b.dim);
+}
+
+// after the last chunk of one source: count[c] += its rows of c (clamped as the scan clamps them), at most capacity
+__global__ void lfb_unpack_commit_kernel(int64_t cells, int capacity, int32_t* count, const int32_t* __restrict__ src_count,
+                                         int src_capacity) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cells) return;
+  int add = src_count[c];
+  add = add < 0 ? 0 : (add > src_capacity ? src_capacity : add);
+  const int64_t n = (int64_t)count[c] + add;
+  count[c] = (int32_t)(n < capacity ? n : capacity);
+}
+
 // ---- non-finite rows ---------------------------------------------------------------------------------------------------
 // a wave per row g = cell * capacity + slot (grid-stride); rows of unoccupied slots are not loaded.  An element is NaN or
 // +-Inf iff its exponent field is all ones; a 32-bit word of a 16-bit bank holds two elements.
@@ -477,6 +516,38 @@ extern "C" int vlfb_lfb_pack(const vlfb_lfb_desc* d, const void* bank, const int
   hipLaunchKernelGGL(lfb_pack_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, b, (const char*)bank, count,
                      offsets, first_row, out, out_dtype, keys);
   return check_launch("lfb_pack");
+}
+
+extern "C" int vlfb_lfb_unpack(const vlfb_lfb_desc* d, void* bank, const int32_t* count, const void* feats, int feat_dtype,
+                               const int32_t* src_count, int src_capacity, const int64_t* src_offsets, int64_t first_row,
+                               int64_t rows, int32_t* dropped, vlfb_stream_t stream) {
+  BankP b;
+  int rc = check_desc(d, &b);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(bank && count && feats && src_count && src_offsets, "lfb_unpack: NULL buffer");
+  VLFB_REQUIRE(dtype_ok(feat_dtype), "lfb_unpack: feature dtype must be f32, bf16 or f16");
+  VLFB_REQUIRE(src_capacity > 0, "lfb_unpack: src_capacity must be positive");
+  VLFB_REQUIRE((int64_t)b.n_videos * b.n_steps <= VLFB_LFB_PACK_MAX_CELLS, "lfb_unpack: more than 2^20 cells (see vlfb_lfb_pack_offsets)");
+  VLFB_REQUIRE(rows >= 0 && rows < (1 << 20), "lfb_unpack: rows out of range");
+  VLFB_REQUIRE(first_row >= 0, "lfb_unpack: first_row is negative");
+  if (rows == 0) return VLFB_OK;
+  hipLaunchKernelGGL(lfb_unpack_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, b, (char*)bank, count, feats,
+                     feat_dtype, src_count, src_capacity, src_offsets, first_row, dropped);
+  return check_launch("lfb_unpack");
+}
+
+extern "C" int vlfb_lfb_unpack_commit(const vlfb_lfb_desc* d, int32_t* count, const int32_t* src_count, int src_capacity,
+                                      vlfb_stream_t stream) {
+  BankP b;
+  int rc = check_desc(d, &b);
+  if (rc != VLFB_OK) return rc;
+  VLFB_REQUIRE(count && src_count, "lfb_unpack_commit: NULL buffer");
+  VLFB_REQUIRE(src_capacity > 0, "lfb_unpack_commit: src_capacity must be positive");
+  const int64_t cells = (int64_t)b.n_videos * b.n_steps;
+  VLFB_REQUIRE(cells <= VLFB_LFB_PACK_MAX_CELLS, "lfb_unpack_commit: more than 2^20 cells (see vlfb_lfb_pack_offsets)");
+  hipLaunchKernelGGL(lfb_unpack_commit_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cells,
+                     b.capacity, count, src_count, src_capacity);
+  return check_launch("lfb_unpack_commit");
 }
 
 extern "C" int vlfb_lfb_count_nonfinite(const vlfb_lfb_desc* d, const void* bank, const int32_t* count, int64_t* out,

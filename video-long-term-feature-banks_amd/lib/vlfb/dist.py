@@ -86,3 +86,19 @@ def gather_rows(t):
     parts = [torch.empty_like(src) for _ in range(world_size())]
     td.all_gather(parts, src)
     return torch.cat(parts).to(t.device)
+
+
+def gather_ragged(t, rows):
+    """the first rows[k] rows of rank k's 2-D tensor, for every rank, as a list in rank order on t.device.  Every rank passes
+    the same `rows` and a `t` of at least max(rows) rows: max(rows) of them travel from each rank (behind its own rows[rank]
+    they are padding, dropped on arrival).  Bytes travel, so the result is bit-exact whatever the element type; on backend
+    nccl they stay on the device, on gloo they go through the host as in `gather_rows`.  [t[:rows[0]]] without a group."""
+    rows = [int(r) for r in rows]
+    if not initialized():
+        return [t[:rows[0]]]
+    assert len(rows) == world_size() and t.dim() == 2 and t.shape[0] >= max(rows), "gather_ragged: rows / tensor mismatch"
+    src = t[:max(rows)].contiguous().view(torch.uint8)
+    src = src if td.get_backend() == "nccl" else src.cpu()
+    parts = [torch.empty_like(src) for _ in range(world_size())]
+    td.all_gather(parts, src)
+    return [p[:r].to(t.device).view(t.dtype) for p, r in zip(parts, rows)]

@@ -272,6 +272,8 @@ _SIGS = {
     "vlfb_lfb_sample_packed": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, _P, C.c_int, _P]),
     "vlfb_lfb_pack_offsets": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P]),
     "vlfb_lfb_pack": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, _I64, _P, C.c_int, _P, _P]),
+    "vlfb_lfb_unpack": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, C.c_int, _P, C.c_int, _P, _I64, _I64, _P, _P]),
+    "vlfb_lfb_unpack_commit": (C.c_int, [C.POINTER(LfbDesc), _P, _P, C.c_int, _P]),
     "vlfb_lfb_count_nonfinite": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _P]),
     "vlfb_topk_hits": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, C.c_int, _P, _P]),
     "vlfb_topk_hits_keep": (C.c_int, [_P, C.c_int, _P, _I64, _I64, _P, C.c_int, _P, _P, _P, _I64, _P, _P]),

@@ -10,8 +10,8 @@ Here the bank lives in HBM for the whole job (AVA train: 235 videos x 900 s x 16
 = 13.9 GB of the 288 GB), `box_pooled` is appended to it by a kernel without leaving the device,
 and the sampled (R, K, 2048) block is written by a kernel straight into the model's `lfb` input.
 `from_reference` / `to_reference` convert to and from the reference's pickled dictionaries.  Whatever leaves the bank
-(`to_reference`, `save`, `merge_from`) reads it through `packed_chunks`: the occupied rows only, in cell order, one staging
-chunk at a time (vlfb_lfb_pack_offsets / vlfb_lfb_pack), never a dense copy.
+(`to_reference`, `save`, `merge_from`, `all_gather_ranks`) reads it through `packed_chunks`: the occupied rows only, in cell
+order, one staging chunk at a time (vlfb_lfb_pack_offsets / vlfb_lfb_pack), never a dense copy.
 
 All compute goes through libvlfb_hip.so (vlfb_lfb_*); there is no host fallback.
 """
@@ -438,11 +438,14 @@ class DeviceBank(object):
     # ---- packed export: only occupied rows move ---------------------------------------------------
     MERGE_ROWS = 4096   # rows of one append in merge_from / load: lfb_commit_kernel is quadratic in the rows of a call
 
-    def pack_offsets(self):
+    def pack_offsets(self, count=None):
         """int64 (cells + 1,) device tensor of vlfb_lfb_pack_offsets: the packed row at which every cell starts; the last
-        entry is the number of features the bank holds"""
+        entry is the number of features the bank holds.  `count`: another int32 (cells,) device count array of this geometry
+        (another rank's) instead of the bank's own."""
+        count = self.count if count is None else count
+        assert count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == self.count.numel()
         off = torch.empty(self.n_videos * self.n_steps + 1, device=self.device, dtype=torch.int64)
-        hip.call("vlfb_lfb_pack_offsets", C.byref(self.desc), hip.ptr(self.count), hip.ptr(off))
+        hip.call("vlfb_lfb_pack_offsets", C.byref(self.desc), hip.ptr(count), hip.ptr(off))
         return off
 
     def packed_chunks(self, chunk_rows=65536, out_dtype=None):
@@ -461,13 +464,105 @@ class DeviceBank(object):
         keys = torch.empty((rows, 2), device=self.device, dtype=torch.int32)
         for first in range(0, total, chunk_rows):
             n = min(chunk_rows, total - first)
-            hip.call("vlfb_lfb_pack", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(off), first, n,
-                     hip.ptr(feats), hip.dtype_code(dt), hip.ptr(keys))
+            self._pack_enqueue(off, first, n, feats, keys)
             yield feats, keys, n
 
+    def _pack_enqueue(self, off, first, n, feats, keys):
+        hip.call("vlfb_lfb_pack", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(self.count), hip.ptr(off), int(first), int(n),
+                 hip.ptr(feats), hip.dtype_code(feats.dtype), hip.ptr(keys))
+
+    # ---- packed import: rows of another bank's packed order, placed without keys -------------------------------------------
+    def unpack_enqueue(self, feats, src_count, src_offsets, first_row, n, src_capacity=None, base=None):
+        """rows [first_row, first_row + n) of ANOTHER bank's packed order (vlfb_lfb_unpack): `feats` a contiguous (>= n, dim)
+        device tensor of any bank element type, `src_count` / `src_offsets` that bank's int32 count and its `pack_offsets`
+        (device tensors, same n_videos / n_steps / dim), `src_capacity` its capacity (default this bank's).  Row s of a cell
+        goes to slot base[cell] + s, `base` = this bank's count by default; a row past the capacity is counted in `dropped`.
+        The launch only READS the count: every chunk of one source is placed against the same base, and `unpack_commit`
+        publishes the source once, after its last chunk.  One launch on the current stream, nothing allocated, no
+        synchronisation."""
+        assert feats.is_cuda and feats.is_contiguous() and feats.numel() >= int(n) * self.dim
+        base = self.count if base is None else base
+        hip.call("vlfb_lfb_unpack", C.byref(self.desc), hip.ptr(self.bank), hip.ptr(base), hip.ptr(feats),
+                 hip.dtype_code(feats.dtype), hip.ptr(src_count), int(src_capacity or self.capacity), hip.ptr(src_offsets),
+                 int(first_row), int(n), hip.ptr(self.dropped))
+
+    def unpack_commit(self, src_count, src_capacity=None, count=None):
+        """after the last `unpack_enqueue` of one source, ONCE: count = min(count + min(src_count, src_capacity), capacity)
+        (vlfb_lfb_unpack_commit); `count` another int32 count array of this geometry instead of the bank's own"""
+        count = self.count if count is None else count
+        hip.call("vlfb_lfb_unpack_commit", C.byref(self.desc), hip.ptr(count), hip.ptr(src_count),
+                 int(src_capacity or self.capacity))
+
+    def _geometry(self):
+        return (self.n_videos, self.n_steps, self.capacity, self.dim, self.code, self.step_base, self.video_ids)
+
+    def all_gather_ranks(self, chunk_rows=65536):
+        """Every rank's bank becomes the merge of all ranks' banks in rank order -- what rank 0's bank is after merge_from(rank
+        1's), merge_from(rank 2's), ...: in every cell rank 0's rows, then rank 1's, ..., at most `capacity`.  A no-op without
+        a process group.  Collective: every rank calls it, with the same geometry (n_videos, n_steps, capacity, dim, element
+        type, step_base, video_ids; else every rank raises).
+
+        The `count` arrays travel first (cells x 4 bytes per rank); every rank's offsets, totals and the base each rank's rows
+        are placed on (the count after the ranks before it) follow from them, so no keys travel.  Then the packed rows, in
+        rounds of at most `chunk_rows` rows per rank (the staging memory: world x chunk_rows rows); every rank runs the same
+        number of rounds (the largest bank's), a rank with fewer rows sends padding.  The other ranks' chunks are placed with
+        vlfb_lfb_unpack against their bases, and this rank's own rows stay where they are -- unless a rank before it holds
+        rows of the same cells: then all ranks' rows are placed into a bank of the same geometry (one more bank of memory)
+        that is copied back at the end.  Backend nccl: everything stays on the device; gloo: rows go through the host.
+        Ends with check_no_drops: a merge that overflows a cell drops the same rows on every rank, so every rank raises."""
+        import hashlib
+        from vlfb import dist
+        assert 0 < int(chunk_rows) < (1 << 20), "all_gather_ranks: chunk_rows must be in (0, 2^20)"
+        if not dist.initialized():
+            return self
+        world, me = dist.world_size(), dist.rank()
+        digest = np.frombuffer(hashlib.sha256(repr(self._geometry()).encode()).digest(), dtype=np.int64).copy()
+        seen = dist.gather_rows(torch.as_tensor(digest).view(1, -1).to(self.device)).cpu().numpy()
+        if not dist.all_ok(bool((seen == seen[0]).all())):
+            raise hip.VlfbError("all_gather_ranks: the ranks' banks differ in geometry (n_videos, n_steps, capacity, dim, "
+                                "dtype, step_base, video_ids); this rank's: %r" % (self._geometry()[:6],))
+        if world == 1:
+            self.check_no_drops()
+            return self
+        cells = self.n_videos * self.n_steps
+        counts = dist.gather_rows(self.count.view(1, cells)).contiguous()          # [rank][cell]
+        offsets = [self.pack_offsets(counts[k]) for k in range(world)]
+        totals = [int(x) for x in torch.stack([o[-1] for o in offsets]).cpu().tolist()]
+        bases = torch.zeros((world, cells), device=self.device, dtype=torch.int32)
+        merged = torch.zeros(cells, device=self.device, dtype=torch.int32)
+        for k in range(world):                                                     # base of rank k = ranks 0 .. k-1 committed
+            bases[k].copy_(merged)
+            self.unpack_commit(counts[k], count=merged)
+        chunk = min(int(chunk_rows), max(totals))
+        # this rank's rows stay in place where no rank before it holds rows of their cell (base 0: always so when the ranks'
+        # cells are disjoint, as in a sharded pass); otherwise every rank's rows, this one's too, go to a bank of their own
+        # first, since the rows of ranks before this one would land on own rows still to be sent
+        shared = bool(((bases[me] > 0) & (counts[me] > 0)).any().item())
+        dest = self
+        if shared:
+            dest = DeviceBank(self.n_videos, self.n_steps, self.capacity, self.dim, self.bank.dtype, self.device, self.step_base)
+            dest.dropped = self.dropped
+        if chunk:
+            stage = torch.empty((chunk, self.dim), device=self.device, dtype=self.bank.dtype)
+            keys = torch.empty((chunk, 2), device=self.device, dtype=torch.int32)
+            for first in range(0, max(totals), chunk):
+                rows = [max(0, min(chunk, t - first)) for t in totals]
+                if rows[me]:
+                    self._pack_enqueue(offsets[me], first, rows[me], stage, keys)
+                parts = dist.gather_ragged(stage, rows)
+                for k in range(world):
+                    if rows[k] and (k != me or shared):
+                        dest.unpack_enqueue(parts[k], counts[k], offsets[k], first, rows[k], base=bases[k])
+        if shared:
+            self.bank.copy_(dest.bank)
+        self.count.copy_(merged)
+        torch.cuda.current_stream().synchronize()
+        self.check_no_drops()
+        return self
+
     def merge_from(self, other):
-        """append every feature of `other` behind what this bank holds, in `other`'s order (the partial banks of two runs, or
-        of two ranks).  n_steps, dim and step_base must agree, the element type need not; banks that both carry `video_ids`
+        """append every feature of `other` behind what this bank holds, in `other`'s order (the partial banks of two runs; the
+        ranks of a job merge theirs with `all_gather_ranks`).  n_steps, dim and step_base must agree, the element type need not; banks that both carry `video_ids`
         are matched through them, otherwise row by row.  Raises if a feature did not fit."""
         assert (self.n_steps, self.dim, self.step_base) == (other.n_steps, other.dim, other.step_base), \
             "merge_from: banks differ in n_steps / dim / step_base"

@@ -10,6 +10,14 @@ metadata and uploaded in stream order, and the files are written from the bank's
 Charades and EPIC-Kitchens verbs (frame-level banks, construct_frame_level_lfb, :49-76): one `pool5` row per clip, under the
 clip's (video, centre frame); `build_frame_bank` is the same loop on `pool5`.  EPIC nouns have no inference pass: that
 bank comes from detector files and is only loaded.
+
+N ranks (vlfb.dist, one process per GPU) share a pass as the reference's GPUs do (lfb_loader.py:200-223: one RunNet per
+iteration feeds every gpu_k).  The single-process walk issues per-GPU slices of BATCH_SIZE // NUM_GPUS clips; iteration `it`
+of it belongs to rank it % world (`rank_iterations`: slice g of global batch b on gpu_g), each rank appends what it ran to
+its own bank, and DeviceBank.all_gather_ranks makes every rank's bank the merge of all of them.  That merge equals the bank
+of the single-process walk bit for bit: every AVA keyframe (video, second) and every frame-level (video, centre) cell is
+produced by exactly one clip, hence by one rank, so the ranks' cells are disjoint and no order between ranks is ever
+visible; and a test-mode feature does not depend on its batch-mates, while the slices are the same slices.
 """
 import collections
 import os
@@ -20,7 +28,57 @@ import torch
 
 from core.config import config as cfg
 from datasets import ava
+from vlfb import dist, hip
 from vlfb.lfb_bank import DeviceBank
+
+
+def rank_iterations(total, rank, world):
+    """the iterations of a `total`-iteration pass that rank `rank` of `world` runs: it % world == rank, in order (the
+    reference's slice g of global batch b on gpu_g).  The shares are disjoint, cover range(total), differ by at most one."""
+    total, rank, world = int(total), int(rank), int(world)
+    assert total >= 0 and world >= 1 and 0 <= rank < world, (total, rank, world)
+    return list(range(rank, total, world))
+
+
+def pass_iterations(size, per_gpu):
+    """iterations of the single-process walk over `size` clips in slices of `per_gpu` (the last one padded)"""
+    return -(-int(size) // int(per_gpu))
+
+
+def rank_source(source, total, rank=None, world=None):
+    """the items of `source`, a generator of a `total`-iteration pass, at this rank's iterations (`rank_iterations`; default:
+    vlfb.dist's rank and world).  A skipped item is drawn from the source and dropped: what the source draws from its rng
+    per iteration is drawn as in the single-process walk, and since the clips are only (store, video, frames) references
+    -- fetched and decoded by the loader that consumes what is yielded -- a skipped iteration touches no frame."""
+    rank = dist.rank() if rank is None else rank
+    world = dist.world_size() if world is None else world
+    mine = set(rank_iterations(total, rank, world))
+    for it, item in enumerate(source):
+        assert it < total, "the source runs past the pass's %d iterations" % total
+        if it in mine:
+            yield item
+
+
+def check_world():
+    """a pass under a process group: cfg.NUM_GPUS must be its size (the per-GPU slices come from NUM_GPUS)"""
+    if dist.initialized() and dist.world_size() != int(cfg.NUM_GPUS):
+        raise hip.VlfbError("bank pass: %d ranks but cfg.NUM_GPUS = %d (the per-GPU batch and the iterations' owners come "
+                            "from NUM_GPUS)" % (dist.world_size(), int(cfg.NUM_GPUS)))
+
+
+def _on_every_rank(fn):
+    """fn() on this rank, then the outcome agreed by all (dist.all_ok): a rank that failed re-raises, the others raise
+    too instead of waiting for it in the next collective.  fn()'s result, or its exception as is, without a group."""
+    try:
+        out = fn()
+    except Exception:
+        if not dist.initialized():
+            raise
+        dist.all_ok(False)
+        raise
+    if not dist.all_ok(True):
+        raise hip.VlfbError("another rank failed its part of the bank pass")
+    return out
 
 
 def pass_keys(bank, minibatch, meta, rows):
@@ -46,35 +104,42 @@ def build_ava_bank(engine, loader, index, store, bank, rng=None):
     check_decoded at the end.
 
     One deviation from the reference: the clips that pad its last short batch (indices.append(indices[0])) are run and
-    APPENDED again there, so that keyframe's boxes are twice in its pickle.  Here their rows get video -1 and are skipped."""
+    APPENDED again there, so that keyframe's boxes are twice in its pickle.  Here their rows get video -1 and are skipped.
+
+    Under a process group every rank runs its `rank_iterations` of the walk and the banks are merged at the end
+    (DeviceBank.all_gather_ranks): every rank returns the bank of the whole walk (module docstring)."""
+    check_world()
     rng = np.random if rng is None else rng
     metas = collections.deque()                       # the source runs in the loader's thread, one minibatch ahead
+    total = pass_iterations(index.get_db_size(), index.batch_size // cfg.NUM_GPUS)
 
     def source():
-        for args in ava.minibatch_source(index, store, rng):
+        for args in rank_source(ava.minibatch_source(index, store, rng), total):
             metas.append(args[3])
             yield args
 
-    feats, _ = engine.blob_tensor("box_pooled")
-    rows = loader.rows
-    loader.start(source())
-    try:
-        while True:
-            try:
-                mb = loader.next()
-            except StopIteration:
-                break
-            loader.deliver(mb)
-            engine.forward()
-            # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
-            pin = torch.from_numpy(pass_keys(bank, mb, metas.popleft(), rows)).pin_memory()
-            bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
-    finally:
-        loader.stop()
-    torch.cuda.current_stream().synchronize()
-    bank.check_no_drops()
-    store.check_decoded()                             # frames the store decoded from JPEG bytes: none was damaged
-    return bank
+    def run():
+        feats, _ = engine.blob_tensor("box_pooled")
+        rows = loader.rows
+        loader.start(source())
+        try:
+            while True:
+                try:
+                    mb = loader.next()
+                except StopIteration:
+                    break
+                loader.deliver(mb)
+                engine.forward()
+                # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
+                pin = torch.from_numpy(pass_keys(bank, mb, metas.popleft(), rows)).pin_memory()
+                bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
+        finally:
+            loader.stop()
+        torch.cuda.current_stream().synchronize()
+        bank.check_no_drops()
+        store.check_decoded()                         # frames the store decoded from JPEG bytes: none was damaged
+    _on_every_rank(run)
+    return bank.all_gather_ranks()
 
 
 def frame_minibatch_source(index, store, bank_video=None):
@@ -147,36 +212,42 @@ def build_frame_bank(engine, loader, index, store, bank, kind):
     whose rows are the index's video indices (Charades) or carry the video names as `video_ids` (EPIC).  Per batch: next /
     deliver / forward / append_enqueue(pool5); nothing in the loop waits for the device.  At the end one synchronisation,
     check_no_drops, check_finite (a pass has no loss whose NaN guard would notice an overflowed activation) and the store's
-    check_decoded."""
+    check_decoded.  Under a process group: this rank's `rank_iterations` only, then DeviceBank.all_gather_ranks, and
+    check_finite on the merged bank (module docstring)."""
     assert kind in ("charades", "epic_verb"), kind
+    check_world()
     metas = collections.deque()                       # the source runs in the loader's thread, one minibatch ahead
+    total = pass_iterations(index.get_db_size(), index.batch_size // cfg.NUM_GPUS)
 
     def source():
-        for args in frame_minibatch_source(index, store):
+        for args in rank_source(frame_minibatch_source(index, store), total):
             metas.append(args[2])
             yield args
 
-    feats, _ = engine.blob_tensor("pool5")
-    rows = loader.N
-    assert feats.numel() == rows * bank.dim, "pool5 holds %d elements, %d clips x %d planned" % (feats.numel(), rows, bank.dim)
-    loader.start(source())
-    try:
-        while True:
-            try:
-                mb = loader.next()
-            except StopIteration:
-                break
-            loader.deliver(mb)
-            engine.forward()
-            # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
-            pin = torch.from_numpy(frame_pass_keys(bank, kind, metas.popleft(), rows)).pin_memory()
-            bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
-    finally:
-        loader.stop()
-    torch.cuda.current_stream().synchronize()
-    bank.check_no_drops()
+    def run():
+        feats, _ = engine.blob_tensor("pool5")
+        rows = loader.N
+        assert feats.numel() == rows * bank.dim, "pool5 holds %d elements, %d clips x %d planned" % (feats.numel(), rows, bank.dim)
+        loader.start(source())
+        try:
+            while True:
+                try:
+                    mb = loader.next()
+                except StopIteration:
+                    break
+                loader.deliver(mb)
+                engine.forward()
+                # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
+                pin = torch.from_numpy(frame_pass_keys(bank, kind, metas.popleft(), rows)).pin_memory()
+                bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
+        finally:
+            loader.stop()
+        torch.cuda.current_stream().synchronize()
+        bank.check_no_drops()
+        store.check_decoded()                         # frames the store decoded from JPEG bytes: none was damaged
+    _on_every_rank(run)
+    bank.all_gather_ranks()
     bank.check_finite()
-    store.check_decoded()                             # frames the store decoded from JPEG bytes: none was damaged
     return bank
 
 
@@ -220,18 +291,25 @@ def load_lfb(is_train, dtype="bf16", device="cuda:0", capacity=None):
 def write_lfb(bank, is_train, native=True):
     """train_lfb.pkl / val_lfb.pkl under CHECKPOINT.DIR in the reference's format (fp32 features; protocol 2, the highest
     the reference's Python 2 reads) and, next to it, the native .npz `load_lfb` prefers.  Charades and EPIC-verb banks are
-    written as {video: {frame: feat}} with the reference's frame numbers."""
+    written as {video: {frame: feat}} with the reference's frame numbers.  Under a process group every rank holds the merged
+    bank: rank 0 writes, and no rank returns before the files are there (a barrier, dist.all_ok: if rank 0 fails to write,
+    every rank raises)."""
     pkl, npz = lfb_paths(cfg.CHECKPOINT.DIR, is_train)
-    if cfg.DATASET in ("charades", "epic"):
-        if cfg.DATASET == "epic" and cfg.EPIC.CLASS_TYPE == "noun":
-            raise NotImplementedError("write_lfb: an EPIC noun bank comes from detector files, no pass infers one to write")
-        lfb = bank.to_reference(frame_level=True, sample_freq=frame_sample_freq(), epic=cfg.DATASET == "epic")
-    else:
-        lfb = bank.to_reference()
-    with open(pkl, "wb") as f:
-        pickle.dump(lfb, f, 2)
-    if native:
-        bank.save(npz)
+    if cfg.DATASET == "epic" and cfg.EPIC.CLASS_TYPE == "noun":
+        raise NotImplementedError("write_lfb: an EPIC noun bank comes from detector files, no pass infers one to write")
+
+    def write():
+        if dist.rank() != 0:
+            return
+        if cfg.DATASET in ("charades", "epic"):
+            lfb = bank.to_reference(frame_level=True, sample_freq=frame_sample_freq(), epic=cfg.DATASET == "epic")
+        else:
+            lfb = bank.to_reference()
+        with open(pkl, "wb") as f:
+            pickle.dump(lfb, f, 2)
+        if native:
+            bank.save(npz)
+    _on_every_rank(write)
     return pkl
 
 
