@@ -888,6 +888,22 @@ int vlfb_clip_batch_preprocess_indexed(const vlfb_clip_item* items_host, const v
  * vlfb_jpeg_decode_host: the same arithmetic (csrc/vlfb_jpeg_core.h, compiled for the host) for ONE item whose scan and
  * seg_offsets are HOST addresses; single-threaded, allocates its own workspace, needs no GPU.  It is the checker that pins
  * the arithmetic against libjpeg-turbo where no GPU is present, not a loader path.
+ *
+ * vlfb_jpeg_decode_batch_par: as vlfb_jpeg_decode_batch (same items, workspace, status words, argument checks), with the
+ * entropy decode of the items the routing rule accepts -- no restart interval, one segment, a scan of at least two
+ * subsequences and at most 128 KiB (csrc/vlfb_jpeg_core.h, vlfb_jpeg_item_is_parallel) -- done by one workgroup of 256 lanes
+ * per item: the scan is destuffed into LDS, every lane decodes a `subseq_bytes`-byte subsequence from a guessed state, the
+ * lanes resynchronise on their neighbours' exit states (at most 256 rounds per chunk of 256 subsequences: the serial walk
+ * in the worst case, so the result never rests on synchronisation happening), then write the coefficients from their
+ * confirmed states; DC prediction is a prefix sum.  A missing code, a DC size above 15, a run past coefficient 63, a marker
+ * or the end of the data before the last MCU, or any padding bit consumed sends the item to the serial kernel in the same
+ * call, so pixels and status of a damaged stream are those of vlfb_jpeg_decode_batch.  Every other item takes the serial
+ * kernel as before.  subseq_bytes: a multiple of 4 in 8..4096, 0 = the library's default (256).  stats_dev: NULL, or int32
+ * [n_items][4] = {routed (0 serial by rule, 1 parallel, 2 parallel then redone serially), chunks, synchronisation rounds
+ * summed over the chunks, most rounds of one chunk}.
+ * vlfb_jpeg_decode_host_par: the same algorithm on the host for ONE item (host addresses), with `lanes` simulated lanes
+ * per chunk (1..1024) run one after another; stats: NULL or int32 [4] as above.  The checker of the parallel arithmetic
+ * where no GPU is present.
  * ------------------------------------------------------------------------------------------ */
 #define VLFB_JPEG_ITEM_BYTES 1424
 enum { VLFB_JPEG_TRUNCATED = 1, VLFB_JPEG_BAD_CODE = 2, VLFB_JPEG_BAD_RESTART = 4 };
@@ -904,6 +920,11 @@ int64_t vlfb_jpeg_workspace_bytes(const vlfb_jpeg_item* items_host, int n_items)
 int vlfb_jpeg_decode_batch(const vlfb_jpeg_item* items_host, const vlfb_jpeg_item* items_dev, int n_items, void* workspace,
                            int64_t workspace_bytes, int32_t* status_dev, vlfb_stream_t stream);
 int vlfb_jpeg_decode_host(const vlfb_jpeg_item* item, uint8_t* dst, int32_t* status);
+int vlfb_jpeg_decode_batch_par(const vlfb_jpeg_item* items_host, const vlfb_jpeg_item* items_dev, int n_items, void* workspace,
+                               int64_t workspace_bytes, int32_t* status_dev, int subseq_bytes, int32_t* stats_dev,
+                               vlfb_stream_t stream);
+int vlfb_jpeg_decode_host_par(const vlfb_jpeg_item* item, uint8_t* dst, int32_t* status, int lanes, int subseq_bytes,
+                              int32_t* stats);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics on the device.  Replace the host meter of lib/utils/metrics.py, which fetches `pred` and

@@ -8,6 +8,10 @@ size are 30-90 KB), against the decoded-frame feed (`fetch` returning prepared a
   bytes         what slots() copies host-to-device
   PIL           single-thread decode of one file (libjpeg-turbo, the library behind cv2.imread), where PIL is importable
 
+With --par the lane-parallel entry point is measured beside the serial one: vlfb_jpeg_decode_batch_par alone at every
+--subseq size (with its synchronisation counts: chunks, rounds per chunk, items redone serially), and the host time of ONE
+FrameStore.slots_many() for the same 256 missing frames as 8 clips of 32.
+
 Medians of --repeats after --warmup, one process.  With --overlap, tools/loader_overlap.py --jpeg runs afterwards in a
 process of its own (the training step beside a loader whose store is fed these bytes) and its table is appended.
 
@@ -63,6 +67,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--overlap", action="store_true", help="append tools/loader_overlap.py --jpeg")
+    ap.add_argument("--par", action="store_true", help="measure vlfb_jpeg_decode_batch_par and FrameStore.slots_many as well")
+    ap.add_argument("--subseq", type=int, nargs="+", default=[32, 64, 128, 256, 512, 1024],
+                    help="subsequence sizes of the --par sweep (0: the library's default)")
     args = ap.parse_args()
 
     import torch
@@ -80,7 +87,7 @@ def main():
     stream = torch.cuda.Stream(device=dev)
     numbers = list(range(n))
 
-    def feed(jpeg_fed):
+    def feed(jpeg_fed, many=False):
         store = FrameStore(H, W, n, dev, stream)
         if jpeg_fed:
             store.fetch_jpeg = lambda v, f: files[f]
@@ -93,7 +100,10 @@ def main():
             before = store.uploaded_bytes
             ev[0].record(stream)
             t0 = time.perf_counter()
-            store.slots(rep, numbers)                   # a new video every time: all frames are missing
+            if many:                                    # the minibatch as the loader hands it over: 8 clips of 32 frames
+                store.slots_many([(rep, numbers[c:c + 32]) for c in range(0, n, 32)])
+            else:
+                store.slots(rep, numbers)               # a new video every time: all frames are missing
             host.append(time.perf_counter() - t0)
             ev[1].record(stream)
             store.release()
@@ -109,9 +119,9 @@ def main():
     assert torch.equal(store_j.frames, store_d.frames), "the device decode differs from PIL's pixels"
 
     # the decode batch alone: the last chunk's records are still in the ring and on the device
-    parsed = [(f, f, files[f], __import__("datasets.jpeg", fromlist=["parse"]).parse(files[f])) for f in numbers]
+    parsed = [(0, f, f, files[f], __import__("datasets.jpeg", fromlist=["parse"]).parse(files[f])) for f in numbers]
     torch.cuda.synchronize()
-    st, base, nbytes, items = store_j._stage_jpeg(0, parsed)
+    st, base, nbytes, items = store_j._stage_jpeg(parsed)
     j = store_j._jpeg
     import ctypes as C
     with torch.cuda.stream(stream):
@@ -128,6 +138,32 @@ def main():
             decode.append(ev[0].elapsed_time(ev[1]) * 1e-3)
     assert not j["status"][:n].any() and (store_j.frames[5].cpu().numpy() == pixels[5]).all()      # (frame f went to slot f)
 
+    sweep = []
+    if args.par:
+        want = store_j.frames.clone()
+        stats = torch.zeros(n, 4, dtype=torch.int32, device=dev)
+        with torch.cuda.stream(stream):
+            for subseq in args.subseq:
+                times = []
+                for rep in range(args.warmup + args.repeats):
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                    store_j.frames.zero_()
+                    torch.cuda.synchronize()
+                    ev[0].record(stream)
+                    hip.call("vlfb_jpeg_decode_batch_par", C.cast(items, C.c_void_p), j["dev"].data_ptr() + base, n,
+                             j["workspace"].data_ptr(), j["workspace"].numel(), j["status"].data_ptr(), subseq, stats.data_ptr())
+                    ev[1].record(stream)
+                    torch.cuda.synchronize()
+                    times.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+                assert not j["status"][:n].any() and torch.equal(store_j.frames, want), "the parallel decode differs (subseq %d)" % subseq
+                t = stats.cpu().numpy().astype(np.int64)
+                par = t[t[:, 0] > 0]
+                sweep.append((subseq, median_ms(times[args.warmup:]), int((t[:, 0] == 1).sum()), int((t[:, 0] == 2).sum()),
+                              int((t[:, 0] == 0).sum()), float(par[:, 1].mean()) if len(par) else 0.0,
+                              float(par[:, 2].sum()) / max(1, int(par[:, 1].sum())), int(par[:, 3].max()) if len(par) else 0))
+        store_m, host_m, span_m, bytes_m = feed(True, many=True)
+        assert torch.equal(store_m.frames, store_d.frames) and store_m.decode_calls == args.warmup + args.repeats
+
     from PIL import Image
     pil = []
     for f in files[:64]:
@@ -143,6 +179,13 @@ def main():
     print("%-34s %12.3f %12.3f   ms (events around slots() on the store's stream, idle device)" % ("device span: copy (+ decode)", span_j, span_d))
     print("%-34s %12.3f %12s   ms (three launches; events, idle device)" % ("vlfb_jpeg_decode_batch alone", median_ms(decode[args.warmup:]), "-"))
     print("%-34s %12.2f %12.2f   MB per batch" % ("bytes uploaded", bytes_j / 1e6, bytes_d / 1e6))
+    if args.par:
+        print("%-34s %12.3f %12s   ms (8 requests of 32 frames: one copy, one decode call)" % ("host time of ONE slots_many()", host_m, "-"))
+        print("%-34s %12.3f %12s   ms (events around slots_many() on the store's stream, idle device)" % ("device span of it", span_m, "-"))
+        print("vlfb_jpeg_decode_batch_par alone (four launches; events, idle device), per subseq_bytes:")
+        print("  %8s %10s %9s %7s %7s %8s %13s %11s" % ("subseq", "ms", "parallel", "redone", "serial", "chunks", "rounds/chunk", "most rounds"))
+        for row in sweep:
+            print("  %8d %10.3f %9d %7d %7d %8.2f %13.2f %11d" % row)
     print("PIL (libjpeg-turbo) on this host, one thread: %.3f ms per frame (median of 64) = %.0f ms of core time per batch"
           % (median_ms(pil), median_ms(pil) * n))
     print("the device's pixels equal PIL's on all %d frames" % n)

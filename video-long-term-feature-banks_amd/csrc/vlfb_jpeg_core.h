@@ -277,6 +277,210 @@ VLFB_HD int segment_range(const uint8_t* scan, uint32_t scan_bytes, const uint32
   return (int64_t)n_seg != want ? VLFB_JPEG_BAD_RESTART : 0;   // the range is given all the same: the caller may decode it
 }
 
+// ---- lane-parallel entropy decode (vlfb_jpeg_decode_batch_par, vlfb_jpeg_decode_host_par) ---------------------------------
+// The self-synchronising decode of Weissenberger and Schmidt on the DESTUFFED scan: the bytes before the first marker with
+// the zero of every FF 00 pair removed, kept as big-endian 32-bit words, so that a bit position is a plain number every lane
+// shares and any 32 bits of the stream are two word reads.  The stream is cut into subsequences of `subseq_bytes`; a lane
+// walks one subsequence symbol by symbol from a state (bit position, block inside the MCU, zigzag index k; k = 0: a DC
+// symbol comes next) to the first symbol boundary at or past the subsequence's end.  The functions below are one lane's
+// work; the kernel and the host checker differ only in how they run the lanes (side by side / one after another).
+constexpr int PAR_LANES = 256;                       // lanes of the kernel's workgroup = subsequences of one chunk
+constexpr int PAR_SUBSEQ_DEFAULT = 256;              // profiles/jpeg_decode.txt: the sweep this default comes from
+constexpr uint32_t PAR_MAX_SCAN = 128u * 1024u;      // the destuffed scan lives in LDS beside the tables and lane states
+constexpr int32_t PAR_REDO_BIT = 1 << 30;            // private to one call: "decode this item serially"; never left set
+constexpr uint32_t PAR_NO_STATE = 0xffffffffu;       // a walk that met a bad code, a bad run or the end of the data
+
+VLFB_HD bool par_subseq_ok(int subseq_bytes) { return subseq_bytes >= 8 && subseq_bytes <= 4096 && (subseq_bytes & 3) == 0; }
+
+// THE routing rule, read by both entropy kernels and the host checker: one segment without restart intervals, at least two
+// subsequences long, and a scan that fits the LDS buffer.  Everything else is decoded by the serial kernel.
+VLFB_HD bool vlfb_jpeg_item_is_parallel(const vlfb_jpeg_item& it, int subseq_bytes) {
+  return it.restart_interval == 0 && it.n_segments == 1 && it.scan_bytes >= 2u * (uint32_t)subseq_bytes && it.scan_bytes <= PAR_MAX_SCAN;
+}
+// words the destuffed stream of a scan of n bytes takes at most: its bytes, and two words of zeros behind them
+VLFB_HD uint32_t par_stream_words(uint32_t scan_bytes) { return (scan_bytes + 3u) / 4u + 2u; }
+
+// byte i of the scan is a marker (FF not followed by 00, or FF as the last byte): the data ends in front of the first one
+VLFB_HD bool par_is_marker(const uint8_t* scan, uint32_t n, uint32_t i) { return scan[i] == 0xff && (i + 1 >= n || scan[i + 1] != 0); }
+// byte i is the zero of an FF 00 pair.  An FF in front of the first marker is always read as a fresh byte (only zeros are
+// ever skipped), so the byte before decides alone.
+VLFB_HD bool par_is_stuffing(const uint8_t* scan, uint32_t i) { return scan[i] == 0 && i > 0 && scan[i - 1] == 0xff; }
+// byte j of the destuffed stream goes here, so that a native 32-bit read gives the big-endian word
+VLFB_HD uint32_t par_byte_slot(uint32_t j) { return j ^ 3u; }
+
+struct ParState { uint32_t pos, bk; };               // bit position; block * 64 + k.  pos = PAR_NO_STATE: no state (bk = 0)
+VLFB_HD bool par_same(const ParState& a, const ParState& b) { return a.pos == b.pos && a.bk == b.bk; }
+
+struct ParCtx {
+  const uint32_t* words;                             // the destuffed stream, par_stream_words() long
+  uint32_t data_bits;
+  const Huff* tabs;                                  // DC 0, 1, AC 0, 1
+  uint32_t sel;                                      // two bits per block of the MCU: DC table, AC table
+  int32_t mcu_blocks;
+};
+VLFB_HD uint32_t par_table_select(const Geo& g, const uint8_t* td, const uint8_t* ta) {
+  uint32_t sel = 0;
+  int blk = 0;
+  for (int c = 0; c < g.n_comp; ++c)
+    for (int i = 0; i < g.h[c] * g.v[c] && blk < MAX_MCU_BLOCKS; ++i, ++blk) sel |= (uint32_t)((td[c] & 1) | ((ta[c] & 1) << 1)) << (2 * blk);
+  return sel;
+}
+
+// One symbol at bit `pos` of block `blk`, zigzag index k: its code and its value bits are at most 31 bits, one 32-bit look.
+// PAR_SYM_BAD: no such code, a DC size above 15 or a run past coefficient 63 -- an error to the write pass; a speculative
+// walk goes on as *o says (one bit further, or behind the block the run left), which costs it nothing but its guess.
+// PAR_SYM_END: the symbol would use bits past the data.
+enum { PAR_SYM_OK = 0, PAR_SYM_BAD = 1, PAR_SYM_END = 2 };
+struct ParSym { int32_t bits, k_next, at, value; }; // at: the zigzag index `value` belongs to, -1 for none; k_next >= 64: block done
+VLFB_HD int par_symbol(const ParCtx& c, uint32_t pos, int blk, int k, ParSym* o) {
+  if (pos >= c.data_bits) return PAR_SYM_END;
+  o->bits = 1;
+  o->k_next = k;
+  o->at = -1;
+  o->value = 0;
+  const uint32_t w = pos >> 5, sh = pos & 31u;
+  const uint32_t v = (uint32_t)(((((uint64_t)c.words[w] << 32) | c.words[w + 1]) << sh) >> 32);
+  const uint32_t pick = (c.sel >> (2 * blk)) & 3u;
+  const Huff* t = k == 0 ? c.tabs + (pick & 1u) : c.tabs + 2 + (pick >> 1);
+  const uint32_t v16 = v >> 16;
+  const uint32_t e = t->look[v16 >> (16 - LOOK_BITS)];
+  int len = 0, sym = -1;
+  if (e) {
+    len = (int)(e >> 8);
+    sym = (int)(e & 255u);
+  } else {
+    for (int l = LOOK_BITS + 1; l <= 16 && sym < 0; ++l) {
+      const int32_t code = (int32_t)(v16 >> (16 - l));
+      if (code <= t->maxcode[l]) {
+        len = l;
+        sym = t->sym[(t->valoff[l] + code) & 255];
+      }
+    }
+    if (sym < 0) return PAR_SYM_BAD;
+  }
+  int s;
+  if (k == 0) {
+    s = sym;
+    if (s > 15) return PAR_SYM_BAD;
+    o->at = 0;
+    o->k_next = 1;
+  } else {
+    const int r = sym >> 4;
+    s = sym & 15;
+    if (s) {
+      const int kk = k + r;
+      if (kk > 63) {
+        o->bits = len + s;
+        o->k_next = 64;
+        return pos + (uint32_t)o->bits <= c.data_bits ? PAR_SYM_BAD : PAR_SYM_END;
+      }
+      o->at = kk;
+      o->k_next = kk + 1;
+    } else {
+      o->k_next = r == 15 ? k + 16 : 64;             // sixteen zeros, or the end of the block
+    }
+  }
+  if (s) o->value = extend((v << len) >> (32 - s), s);
+  o->bits = len + s;
+  return pos + (uint32_t)o->bits <= c.data_bits ? PAR_SYM_OK : PAR_SYM_END;
+}
+
+// The speculative / synchronising walk of one lane: from `in` to the first symbol boundary at or past end_bit (<= data_bits).
+// A state at or past end_bit passes through; no state, or a walk that meets the end of the data, gives no state.  max_syms: 8 * subseq_bytes, the
+// bits between the subsequence's start (no valid `in` lies before it) and its end.
+VLFB_HD void par_walk(const ParCtx& c, ParState in, uint32_t end_bit, int32_t max_syms, ParState* out, int32_t* mcus) {
+  *mcus = 0;
+  *out = in;
+  if (in.pos == PAR_NO_STATE || in.pos >= end_bit) return;
+  uint32_t pos = in.pos;
+  int blk = (int)(in.bk >> 6), k = (int)(in.bk & 63u);
+  int32_t done = 0;
+  bool ok = blk < c.mcu_blocks;
+  for (int32_t n = 0; ok && n < max_syms && pos < end_bit; ++n) {
+    ParSym s;
+    ok = par_symbol(c, pos, blk, k, &s) != PAR_SYM_END;
+    if (!ok) break;
+    pos += (uint32_t)s.bits;
+    k = s.k_next;
+    if (k >= 64) {
+      k = 0;
+      if (++blk == c.mcu_blocks) { blk = 0; ++done; }
+    }
+  }
+  *mcus = done;                                      // of a failed walk too: the write pass completes the same MCUs before it fails
+  if (!ok || pos < end_bit) {
+    out->pos = PAR_NO_STATE;
+    out->bk = 0;
+    return;
+  }
+  out->pos = pos;
+  out->bk = (uint32_t)(blk * 64 + k);
+}
+// the lanes of a chunk whose subsequence begins inside the data; the others take no part (a state would need a round per lane
+// to pass through them), and the chunk hands on the exit state of its last live lane
+VLFB_HD int32_t par_live_lanes(uint32_t data_bits, uint32_t chunk_start_bit, int32_t lanes, int32_t subseq_bytes) {
+  if (chunk_start_bit >= data_bits) return 0;
+  const uint32_t bits = 8u * (uint32_t)subseq_bytes, live = (data_bits - chunk_start_bit + bits - 1u) / bits;
+  return live < (uint32_t)lanes ? (int32_t)live : lanes;
+}
+
+// The write pass of one lane: the same walk from its CONFIRMED start state, whose MCU is `mcu`, into the cleared coefficient
+// area: every non-zero AC coefficient, and each block's DC DIFFERENCE at index 0.  false: the item must be decoded serially.
+VLFB_HD bool par_write(const ParCtx& c, const Geo& g, ParState in, uint32_t end_bit, int32_t max_syms, int64_t mcu, int64_t total,
+                       uint8_t* ws) {
+  if (mcu >= total) return true;                     // behind the last MCU: whatever follows is no error
+  if (in.pos == PAR_NO_STATE) return false;
+  if (in.pos >= end_bit) return true;
+  uint32_t pos = in.pos;
+  int blk = (int)(in.bk >> 6), k = (int)(in.bk & 63u);
+  if (blk >= c.mcu_blocks) return false;
+  int comp;
+  int64_t block;
+  mcu_block_place(g, mcu, blk, &comp, &block);
+  int16_t* out = reinterpret_cast<int16_t*>(ws + coef_offset(g, comp) + block * 128);
+  for (int32_t n = 0; n < max_syms && pos < end_bit; ++n) {
+    ParSym s;
+    if (par_symbol(c, pos, blk, k, &s) != PAR_SYM_OK) return false;
+    if (s.at >= 0 && s.value != 0) out[natural_order(s.at)] = (int16_t)s.value;
+    pos += (uint32_t)s.bits;
+    k = s.k_next;
+    if (k >= 64) {
+      k = 0;
+      if (++blk == c.mcu_blocks) {
+        blk = 0;
+        if (++mcu >= total) return true;
+      }
+      mcu_block_place(g, mcu, blk, &comp, &block);
+      out = reinterpret_cast<int16_t*>(ws + coef_offset(g, comp) + block * 128);
+    }
+  }
+  return pos >= end_bit;
+}
+
+// DC prediction as a prefix sum of the differences in decode order, modulo 2^16 (the serial (int16_t)(pred + diff) wraps the
+// same way, and the wrap is associative).  sum: the differences of MCUs [m0, m1) per component; apply: the coefficients of
+// those MCUs from pred[], the sums of everything before m0.
+VLFB_HD void par_dc_sum(const Geo& g, const uint8_t* ws, int64_t m0, int64_t m1, uint32_t* sums) {
+  for (int64_t m = m0; m < m1; ++m)
+    for (int b = 0; b < g.mcu_blocks && b < MAX_MCU_BLOCKS; ++b) {
+      int comp;
+      int64_t block;
+      mcu_block_place(g, m, b, &comp, &block);
+      sums[comp] += (uint32_t)(int32_t) * reinterpret_cast<const int16_t*>(ws + coef_offset(g, comp) + block * 128);
+    }
+}
+VLFB_HD void par_dc_apply(const Geo& g, uint8_t* ws, int64_t m0, int64_t m1, uint32_t* pred) {
+  for (int64_t m = m0; m < m1; ++m)
+    for (int b = 0; b < g.mcu_blocks && b < MAX_MCU_BLOCKS; ++b) {
+      int comp;
+      int64_t block;
+      mcu_block_place(g, m, b, &comp, &block);
+      int16_t* p = reinterpret_cast<int16_t*>(ws + coef_offset(g, comp) + block * 128);
+      pred[comp] += (uint32_t)(int32_t)*p;
+      *p = (int16_t)(uint16_t)(pred[comp] & 0xffffu);
+    }
+}
+
 // ---- inverse DCT: jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2) ----------------------------------------------------------
 // one pass over eight values: out = (x + 2^(shift - 1)) >> shift.  64-bit intermediates as libjpeg's JLONG, so that no stream
 // can overflow them; on coefficients a real encoder writes they equal the 32-bit ones.

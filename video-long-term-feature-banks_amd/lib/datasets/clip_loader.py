@@ -155,15 +155,21 @@ class ClipSlots(object):
         sizes, ptrs, keep, used, stores, staged = [], [], [], 0, [], {}
         s.keep, s.stores = keep, stores
         index = s.pin_index.numpy().reshape(self.N, T)
-        for i, f in enumerate(frames_list):
-            if forms[i]:
+        for i, f in enumerate(frames_list):            # the frame-list clips of one store: ONE slots_many, so one upload and
+            if forms[i]:                               # one decode call per store and minibatch
                 store, video, numbers = f
                 assert store.stream is self.stream and store.device == self.device, \
                     "the frame store must be built on this loader's stream and device"
                 assert len(numbers) == T, "clips of %d frames" % T
                 if not any(store is x for x in stores):
                     stores.append(store)
-                index[i] = store.slots(video, numbers)
+        for store in list(stores):
+            mine = [i for i, f in enumerate(frames_list) if forms[i] and f[0] is store]
+            for i, slots in zip(mine, store.slots_many([(frames_list[i][1], frames_list[i][2]) for i in mine])):
+                index[i] = slots
+        for i, f in enumerate(frames_list):
+            if forms[i]:
+                store = f[0]
                 s.store_frames[i] = store.capacity
                 sizes.append((store.height, store.width))
                 ptrs.append(store.data_ptr())

@@ -14,7 +14,8 @@ the clip through a table of slot numbers (vlfb_clip_batch_preprocess_indexed).
 
 Compressed frames: with `store.fetch_jpeg = read` (read(video, frame_number) -> the bytes of a baseline JPEG file) the
 store parses each missing file on the host (datasets.jpeg), uploads the scan bytes and one record per frame in ONE copy and
-decodes them on its stream into their slots (vlfb_jpeg_decode_batch: bit for bit what cv2.imread returns).  A file the
+decodes them on its stream into their slots (vlfb_jpeg_decode_batch_par: bit for bit what cv2.imread returns); `slots_many`
+does this once for all the clips of a minibatch.  A file the
 decoder does not take (datasets.jpeg.JpegUnsupported: progressive, CMYK, ...) goes through `fetch` when that is set as
 well; a file of another size than the store's is refused like a failing `fetch`.  What the device finds in a damaged
 stream comes back through `check_decoded()`, to be called where the caller synchronises anyway.
@@ -52,29 +53,38 @@ class StoreIndex(object):
     def assign(self, video, frame_numbers):
         """-> (slot of every requested frame, [(frame number, slot)] of those that must be uploaded, in request order).
         A request the store cannot hold is refused whole: VlfbError, and the bookkeeping is what it was before the call."""
+        return self.assign_many([(video, frame_numbers)])[0]
+
+    def assign_many(self, requests):
+        """`assign` for the requests [(video, frame_numbers), ...] of one minibatch -> [(slots, missing)] per request; a
+        frame several requests name is missing in the first of them only.  ONE snapshot, taken before the first request:
+        a refusal of any request, and `undo`, take all of them back."""
         self._before = (self.slot_of.copy(), list(self.free), set(self.open), self.fetched, self.requested)
-        slots, missing = [], []
+        out = []
         try:
-            for f in frame_numbers:
-                key = (video, int(f))
-                slot = self.slot_of.get(key)
-                if slot is None:
-                    slot = self._take()
-                    self.slot_of[key] = slot
-                    missing.append((int(f), slot))
-                self.open.add(key)
-                slots.append(slot)
+            for video, frame_numbers in requests:
+                slots, missing = [], []
+                for f in frame_numbers:
+                    key = (video, int(f))
+                    slot = self.slot_of.get(key)
+                    if slot is None:
+                        slot = self._take()
+                        self.slot_of[key] = slot
+                        missing.append((int(f), slot))
+                    self.open.add(key)
+                    slots.append(slot)
+                self.requested += len(slots)
+                self.fetched += len(missing)
+                out.append((slots, missing))
         except hip.VlfbError:
             self.undo()
             raise
-        self.requested += len(slots)
-        self.fetched += len(missing)
-        return slots, missing
+        return out
 
     def undo(self):
-        """take the last `assign` back (it was refused, or a frame it asked for could not be fetched) before anything was
-        uploaded: what it evicted is resident again -- the device still holds those bytes --, what it opened is not open,
-        and nothing of it is counted"""
+        """take the last `assign` / `assign_many` back (it was refused, or a frame it asked for could not be fetched) before
+        anything was uploaded: what it evicted is resident again -- the device still holds those bytes --, what it opened
+        is not open, and nothing of it is counted"""
         self.slot_of, self.free, self.open, self.fetched, self.requested = self._before
         self._before = None
 
@@ -95,16 +105,20 @@ class StoreIndex(object):
 
 
 class FrameStore(object):
-    def __init__(self, height, width, capacity, device, stream, staging_buffers=2):
+    def __init__(self, height, width, capacity, device, stream, staging_buffers=2, jpeg_subseq_bytes=None):
         """a ring of `capacity` uint8 BGR frames (height, width, 3) on `device`; `stream` is the stream of the loader
-        whose launches read it"""
+        whose launches read it.  jpeg_subseq_bytes: the subsequence size of the lane-parallel JPEG decode
+        (vlfb_jpeg_decode_batch_par; None: the library's default), -1: the serial vlfb_jpeg_decode_batch"""
         self.height, self.width, self.capacity = int(height), int(width), int(capacity)
         self.device, self.stream = torch.device(device), stream
         self.fetch = None                              # the default `fetch` of `slots`: set it before clips name this store
         self.fetch_jpeg = None                         # f(video, frame_number) -> JPEG bytes, decoded on the device
         self._jpeg = None                              # rings, workspace and status log of the JPEG path: on its first use
         self._jpeg_staging_buffers = int(staging_buffers)
+        self.jpeg_subseq_bytes = None if jpeg_subseq_bytes is None else int(jpeg_subseq_bytes)
         self.uploaded_bytes = 0                        # bytes copied host-to-device so far, either way
+        self.decode_calls = 0                          # JPEG decode calls enqueued so far: one per minibatch that missed a file
+        self.decoded_frames = 0                        # frames they decoded
         self.index = StoreIndex(capacity)
         self.frames = torch.zeros(self.capacity, self.height, self.width, 3, dtype=torch.uint8, device=self.device)
         # the fill runs on the constructing thread's current stream, which `stream` does not follow by itself: without this
@@ -167,18 +181,18 @@ class FrameStore(object):
             st["used"], st["in_flight"] = 0, False
         return st
 
-    def _stage_jpeg(self, video, parsed):
-        """records, segment tables and scan bytes of `parsed` [(frame number, slot, file bytes, JpegInfo)] into the ring;
+    def _stage_jpeg(self, parsed):
+        """records, segment tables and scan bytes of `parsed` [(video, frame number, slot, file bytes, JpegInfo)] into the ring;
         -> (buffer, first byte, bytes, item array) of the chunk to upload"""
         j, n = self._jpeg, len(parsed)
         if j["logged"] + n > self.JPEG_STATUS_LOG:
             self.check_decoded()                       # the log is full: one wait per JPEG_STATUS_LOG decoded frames
         rec = -(-n * hip.JPEG_ITEM_BYTES // 16) * 16
         seg_at, scan_at, at = [], [], rec
-        for _, _, _, info in parsed:
+        for _, _, _, _, info in parsed:
             seg_at.append(at)
             at += -(-4 * len(info.segment_offsets) // 16) * 16
-        for _, _, _, info in parsed:
+        for _, _, _, _, info in parsed:
             scan_at.append(at)
             at += -(-max(info.scan_bytes, 1) // 16) * 16
         st = self._jpeg_buffer_for(at)
@@ -186,7 +200,7 @@ class FrameStore(object):
         dev = j["dev"].data_ptr() + base
         items = (hip.JpegItem * n).from_buffer(st["np"], base)
         ws = 0
-        for k, (_, slot, data, info) in enumerate(parsed):
+        for k, (_, _, slot, data, info) in enumerate(parsed):
             it = info.fill(items[k])
             it.scan, it.seg_offsets = dev + scan_at[k], dev + seg_at[k]
             it.dst = self.frames.data_ptr() + slot * self.frame_bytes
@@ -226,41 +240,50 @@ class FrameStore(object):
         """the slot of every frame of `frame_numbers` of `video`; the frames that are not resident are fetched and uploaded
         on the store's stream: decoded by `fetch(video, frame_number)` (default: self.fetch; runs of adjacent slots in one
         copy), or, when `fetch` is not given and self.fetch_jpeg is set, as JPEG bytes decoded on the device"""
+        return self.slots_many([(video, frame_numbers)], fetch=fetch)[0]
+
+    def slots_many(self, requests, fetch=None):
+        """`slots` for the requests [(video, frame_numbers), ...] of one minibatch -> one slot list per request.  A frame
+        several requests share is fetched once; all missing JPEG files of all requests are ONE chunk of the ring (one copy,
+        one decode call), all frames that go through `fetch` one staging pass.  All or nothing: a request the store
+        cannot hold, a file of another size, a failing `fetch` or an unsupported file without `fetch` raises, enqueues
+        nothing and leaves the index as it was before the call."""
         as_jpeg = fetch is None and self.fetch_jpeg is not None
         fetch = fetch if fetch is not None else self.fetch
-        slots, missing = self.index.assign(video, frame_numbers)
+        assigned = self.index.assign_many(requests)
+        missing = [(video, f, slot) for (video, _), (_, miss) in zip(requests, assigned) for f, slot in miss]
         if missing:
             parsed, chunk = [], None
             try:
                 if as_jpeg:
                     self._jpeg_state()
                     decoded = []
-                    for f, slot in missing:
+                    for video, f, slot in missing:
                         data = self.fetch_jpeg(video, f)
                         try:
                             info = jpeg.parse(data)
                         except jpeg.JpegUnsupported:
                             if fetch is None:
                                 raise
-                            decoded.append((f, slot))  # a file the device does not take: decoded by `fetch`, as today
+                            decoded.append((video, f, slot))  # a file the device does not take: decoded by `fetch`
                             continue
                         if (info.height, info.width) != (self.height, self.width):
                             raise hip.VlfbError("frame store: frame %r of %r is %d x %d, the store holds %d x %d"
                                                 % (f, video, info.height, info.width, self.height, self.width))
-                        parsed.append((f, slot, data, info))
+                        parsed.append((video, f, slot, data, info))
                     missing = decoded
                     if parsed:
-                        chunk = self._stage_jpeg(video, parsed)
+                        chunk = self._stage_jpeg(parsed)
                 if missing:
                     st = self._staging_for(len(missing))
                     base = st["used"]
-                    for k, (f, _) in enumerate(missing):
+                    for k, (video, f, _) in enumerate(missing):
                         a = np.asarray(fetch(video, f))
                         assert a.dtype == np.uint8 and a.shape == (self.height, self.width, 3), \
                             "fetch must return (%d, %d, 3) uint8" % (self.height, self.width)
                         np.copyto(st["np"][base + k], a)
                 if chunk is not None:
-                    self._enqueue_jpeg(video, parsed, *chunk)
+                    self._enqueue_jpeg(parsed, *chunk)
             except BaseException:
                 self.index.undo()                      # nothing was uploaded yet: the store is what it was
                 raise
@@ -269,17 +292,17 @@ class FrameStore(object):
                     k = 0
                     while k < len(missing):
                         run = 1
-                        while k + run < len(missing) and missing[k + run][1] == missing[k][1] + run:
+                        while k + run < len(missing) and missing[k + run][2] == missing[k][2] + run:
                             run += 1
-                        s0 = missing[k][1]
+                        s0 = missing[k][2]
                         self.frames[s0:s0 + run].copy_(st["pin"][base + k:base + k + run], non_blocking=True)
                         k += run
                     st["done"].record(self.stream)
                 st["used"], st["in_flight"] = base + len(missing), True
                 self.uploaded_bytes += len(missing) * self.frame_bytes
-        return slots
+        return [slots for slots, _ in assigned]
 
-    def _enqueue_jpeg(self, video, parsed, st, base, nbytes, items):
+    def _enqueue_jpeg(self, parsed, st, base, nbytes, items):
         """one copy of the chunk and one decode of its frames into their slots, on the store's stream.  A batch the entry
         point refuses is refused before it launches anything: no slot has changed."""
         j, n = self._jpeg, len(parsed)
@@ -289,12 +312,18 @@ class FrameStore(object):
             j["dev"][base:base + nbytes].copy_(st["pin"][base:base + nbytes], non_blocking=True)
             st["done"].record(self.stream)
             st["used"], st["in_flight"] = base + nbytes, True
-            hip.call("vlfb_jpeg_decode_batch", C.cast(items, C.c_void_p), j["dev"].data_ptr() + base, n,
-                     j["workspace"].data_ptr(), j["workspace"].numel(), j["status"].data_ptr() + 4 * first)
+            head = (C.cast(items, C.c_void_p), j["dev"].data_ptr() + base, n, j["workspace"].data_ptr(), j["workspace"].numel(),
+                    j["status"].data_ptr() + 4 * first)
+            if self.jpeg_subseq_bytes == -1:
+                hip.call("vlfb_jpeg_decode_batch", *head)
+            else:
+                hip.call("vlfb_jpeg_decode_batch_par", *(head + (self.jpeg_subseq_bytes or 0, None)))
         with j["lock"]:
-            j["pending"].append((first, [(video, f) for f, _, _, _ in parsed]))
+            j["pending"].append((first, [(video, f) for video, f, _, _, _ in parsed]))
             j["logged"] = first + n
         self.uploaded_bytes += nbytes
+        self.decode_calls += 1
+        self.decoded_frames += n
 
     def release(self):
         self.index.release()

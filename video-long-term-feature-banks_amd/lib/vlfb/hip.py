@@ -263,6 +263,8 @@ _SIGS = {
     "vlfb_jpeg_workspace_bytes": (_I64, [_P, C.c_int]),
     "vlfb_jpeg_decode_batch": (C.c_int, [_P, _P, C.c_int, _P, _I64, _P, _P]),
     "vlfb_jpeg_decode_host": (C.c_int, [_P, _P, _P]),
+    "vlfb_jpeg_decode_batch_par": (C.c_int, [_P, _P, C.c_int, _P, _I64, _P, C.c_int, _P, _P]),
+    "vlfb_jpeg_decode_host_par": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     "vlfb_lfb_bank_bytes": (_I64, [C.POINTER(LfbDesc)]),
     "vlfb_lfb_append": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, C.c_int, _P, _I64, _P, _P]),
     "vlfb_lfb_sample_window": (C.c_int, [C.POINTER(LfbDesc), _P, _P, _P, _I64, C.c_int, C.c_int, C.c_uint64,

@@ -290,7 +290,9 @@ class AvaMultiCropPass(object):
             for i, f in enumerate(frames_list):
                 assert isinstance(f, tuple) and len(f) == 3 and f[0] is store, "clips are (store, video, frame_numbers) of the pass's store"
                 assert len(f[2]) == T, "clips of %d frames" % T
-                index[i] = store.slots(f[1], f[2])     # decode / upload what is not resident, once for the 18 views
+            # decode / upload what is not resident: once for the 18 views, in one call for the minibatch
+            for i, slots in enumerate(store.slots_many([(f[1], f[2]) for f in frames_list])):
+                index[i] = slots
             sizes = [(store.height, store.width)] * N
             ptrs = [store.data_ptr()] * N
             norm = [np.asarray(b, dtype=np.float64).reshape(-1, 4) for b in boxes_list]
