@@ -68,7 +68,7 @@ class Minibatch(object):
     """what `submit` returns: the slot that holds the minibatch on the device, and what the host keeps of it -- `boxes` per
     clip as transformed, `proposals` (rows, 5) / `labels` (rows, classes) as uploaded (padded to the plan; `used` rows are
     real), `original_boxes` (used, 5) and `metadata` (used, 4) = [video, sec, height, width] as ava_data_input.py:180-189
-    builds them for the AVA meter.  Stays valid after the slot has moved on."""
+    builds them for the AVA meter; `meta`, the dict that was submitted with it.  Stays valid after the slot has moved on."""
 
     def __init__(self, slot):
         self.slot, self.index, self.serial = slot, slot.index, slot.serial
@@ -353,6 +353,7 @@ class MinibatchLoader(ClipSlots):
             s.pin_query.numpy()[:3 * rows] = q.reshape(-1)
         # what the host keeps (ava_data_input.py:172-204)
         mb = Minibatch(s)
+        mb.meta = meta
         mb.boxes, mb.proposals, mb.labels, mb.used = boxes, props, labels, rows
         mb.original_boxes = np.concatenate(
             [np.concatenate([np.full((len(b), 1), i, dtype=np.float64), b], axis=1) for i, b in enumerate(norm) if b is not None]
@@ -447,6 +448,7 @@ class FrameLoader(ClipSlots):
         if self.bank is not None:
             s.pin_query.numpy()[:] = self._query(videos, centers).reshape(-1)
         mb = Minibatch(s)
+        mb.meta = meta
         mb.labels, mb.videos, mb.centers, mb.iteration = labels, videos, centers, meta.get("iteration")
 
         with torch.cuda.stream(self.stream):

@@ -8,8 +8,11 @@ metadata and uploaded in stream order, and the files are written from the bank's
     bank = get_lfb(cfg.LFB.MODEL_PARAMS_FILE, is_train=True, store=make_store)     # a DeviceBank, built, loaded or both
 
 Charades and EPIC-Kitchens verbs (frame-level banks, construct_frame_level_lfb, :49-76): one `pool5` row per clip, under the
-clip's (video, centre frame); `build_frame_bank` is the same loop on `pool5`.  EPIC nouns have no inference pass: that
+clip's (video, centre frame); `build_frame_bank` is the same pass on `pool5`.  EPIC nouns have no inference pass: that
 bank comes from detector files and is only loaded.
+
+The loop itself is vlfb.passes.run_pass, which the test and evaluation passes share; what a bank pass adds is the append
+behind every forward (`_bank_pass`), with keys from the `meta` that the Minibatch carries over from the source.
 
 N ranks (vlfb.dist, one process per GPU) share a pass as the reference's GPUs do (lfb_loader.py:200-223: one RunNet per
 iteration feeds every gpu_k).  The single-process walk issues per-GPU slices of BATCH_SIZE // NUM_GPUS clips; iteration `it`
@@ -19,7 +22,6 @@ of the single-process walk bit for bit: every AVA keyframe (video, second) and e
 produced by exactly one clip, hence by one rank, so the ranks' cells are disjoint and no order between ranks is ever
 visible; and a test-mode feature does not depend on its batch-mates, while the slices are the same slices.
 """
-import collections
 import os
 import pickle
 
@@ -28,7 +30,7 @@ import torch
 
 from core.config import config as cfg
 from datasets import ava
-from vlfb import dist, hip
+from vlfb import dist, hip, passes
 from vlfb.lfb_bank import DeviceBank
 
 
@@ -96,50 +98,46 @@ def pass_keys(bank, minibatch, meta, rows):
     return bank.append_keys(videos, secs)
 
 
+def _bank_pass(engine, loader, index, store, bank, source, blob, rows, keys, check_finite):
+    """the bank-construction pass: this rank's iterations (`rank_source`) of `source`, the single-process walk over `index`,
+    through passes.run_pass, and behind every forward the first `rows` rows of `blob` appended to `bank` under keys(mb),
+    the (rows, 2) int32 append keys, uploaded in stream order.  Then check_no_drops; under a process group the outcome
+    agreed by all ranks and DeviceBank.all_gather_ranks, whose result is returned; with check_finite, no NaN / Inf row in
+    the merged bank (a pass has no loss whose NaN guard would notice an overflowed activation)."""
+    check_world()
+    total = pass_iterations(index.get_db_size(), index.batch_size // cfg.NUM_GPUS)
+
+    def run():
+        feats, _ = engine.blob_tensor(blob)
+
+        def append(it, mb):
+            # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
+            pin = torch.from_numpy(keys(mb)).pin_memory()
+            bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
+        passes.run_pass(engine, loader, store, rank_source(source, total), each=append)
+        bank.check_no_drops()
+    _on_every_rank(run)
+    merged = bank.all_gather_ranks()
+    if check_finite:
+        merged.check_finite()
+    return merged
+
+
 def build_ava_bank(engine, loader, index, store, bank, rng=None):
     """the loop of tools/lfb_loader.py:200-223 for AVA: `engine` an lfb_infer_only engine planned in test mode, `loader` its
     MinibatchLoader, `index` an lfb_infer_only datasets.ava.AvaIndex, `store` the FrameStore (on the loader's stream) whose
-    `fetch` decodes, `bank` a DeviceBank whose rows are the index's video indices.  Per batch: next / deliver / forward /
-    append_enqueue(box_pooled); nothing in the loop waits for the device, one synchronisation, check_no_drops and the store's
-    check_decoded at the end.
+    `fetch` decodes, `bank` a DeviceBank whose rows are the index's video indices.  `_bank_pass` on `box_pooled` with
+    `pass_keys`.
 
     One deviation from the reference: the clips that pad its last short batch (indices.append(indices[0])) are run and
     APPENDED again there, so that keyframe's boxes are twice in its pickle.  Here their rows get video -1 and are skipped.
 
     Under a process group every rank runs its `rank_iterations` of the walk and the banks are merged at the end
     (DeviceBank.all_gather_ranks): every rank returns the bank of the whole walk (module docstring)."""
-    check_world()
-    rng = np.random if rng is None else rng
-    metas = collections.deque()                       # the source runs in the loader's thread, one minibatch ahead
-    total = pass_iterations(index.get_db_size(), index.batch_size // cfg.NUM_GPUS)
-
-    def source():
-        for args in rank_source(ava.minibatch_source(index, store, rng), total):
-            metas.append(args[3])
-            yield args
-
-    def run():
-        feats, _ = engine.blob_tensor("box_pooled")
-        rows = loader.rows
-        loader.start(source())
-        try:
-            while True:
-                try:
-                    mb = loader.next()
-                except StopIteration:
-                    break
-                loader.deliver(mb)
-                engine.forward()
-                # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
-                pin = torch.from_numpy(pass_keys(bank, mb, metas.popleft(), rows)).pin_memory()
-                bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
-        finally:
-            loader.stop()
-        torch.cuda.current_stream().synchronize()
-        bank.check_no_drops()
-        store.check_decoded()                         # frames the store decoded from JPEG bytes: none was damaged
-    _on_every_rank(run)
-    return bank.all_gather_ranks()
+    source = ava.minibatch_source(index, store, np.random if rng is None else rng)
+    rows = loader.rows
+    return _bank_pass(engine, loader, index, store, bank, source, "box_pooled", rows,
+                      lambda mb: pass_keys(bank, mb, mb.meta, rows), False)
 
 
 def frame_minibatch_source(index, store, bank_video=None):
@@ -209,45 +207,14 @@ def build_frame_bank(engine, loader, index, store, bank, kind):
     """the loop of tools/lfb_loader.py:200-223 for Charades (`kind` "charades") and EPIC verbs ("epic_verb"): `engine` an
     lfb_infer_only basic-head engine planned in test mode, `loader` its FrameLoader, `index` an lfb_infer_only CharadesIndex
     / EpicIndex, `store` the FrameStore (on the loader's stream) whose `fetch` decodes, `bank` a DeviceBank of capacity 1
-    whose rows are the index's video indices (Charades) or carry the video names as `video_ids` (EPIC).  Per batch: next /
-    deliver / forward / append_enqueue(pool5); nothing in the loop waits for the device.  At the end one synchronisation,
-    check_no_drops, check_finite (a pass has no loss whose NaN guard would notice an overflowed activation) and the store's
-    check_decoded.  Under a process group: this rank's `rank_iterations` only, then DeviceBank.all_gather_ranks, and
-    check_finite on the merged bank (module docstring)."""
+    whose rows are the index's video indices (Charades) or carry the video names as `video_ids` (EPIC).  `_bank_pass` on
+    `pool5` with `frame_pass_keys`, and check_finite on the merged bank."""
     assert kind in ("charades", "epic_verb"), kind
-    check_world()
-    metas = collections.deque()                       # the source runs in the loader's thread, one minibatch ahead
-    total = pass_iterations(index.get_db_size(), index.batch_size // cfg.NUM_GPUS)
-
-    def source():
-        for args in rank_source(frame_minibatch_source(index, store), total):
-            metas.append(args[2])
-            yield args
-
-    def run():
-        feats, _ = engine.blob_tensor("pool5")
-        rows = loader.N
-        assert feats.numel() == rows * bank.dim, "pool5 holds %d elements, %d clips x %d planned" % (feats.numel(), rows, bank.dim)
-        loader.start(source())
-        try:
-            while True:
-                try:
-                    mb = loader.next()
-                except StopIteration:
-                    break
-                loader.deliver(mb)
-                engine.forward()
-                # pinned and device buffers of the caching allocators: reused only behind the copy / the append, no waiting
-                pin = torch.from_numpy(frame_pass_keys(bank, kind, metas.popleft(), rows)).pin_memory()
-                bank.append_enqueue(feats, pin.to(bank.device, non_blocking=True), rows)
-        finally:
-            loader.stop()
-        torch.cuda.current_stream().synchronize()
-        bank.check_no_drops()
-        store.check_decoded()                         # frames the store decoded from JPEG bytes: none was damaged
-    _on_every_rank(run)
-    bank.all_gather_ranks()
-    bank.check_finite()
+    rows = loader.N
+    planned = engine.blob_tensor("pool5")[0].numel()
+    assert planned == rows * bank.dim, "pool5 holds %d elements, %d clips x %d planned" % (planned, rows, bank.dim)
+    _bank_pass(engine, loader, index, store, bank, frame_minibatch_source(index, store), "pool5", rows,
+               lambda mb: frame_pass_keys(bank, kind, mb.meta, rows), True)
     return bank
 
 
@@ -313,41 +280,82 @@ def write_lfb(bank, is_train, native=True):
     return pkl
 
 
-def get_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capacity=None, device="cuda:0", n_slots=2,
-            max_src_hw=(256, 340), rng=None):
-    """lfb_loader.get_lfb: the bank loaded from LFB.LOAD_LFB_PATH when LFB.LOAD_LFB, else inferred with the baseline
-    parameters `params_file` over every keyframe of the train (is_train) or test LFB box lists, and written when
-    LFB.WRITE_LFB.  `store(device, stream)` builds the datasets.frame_store.FrameStore (with its `fetch`) on the loader's
-    stream; `max_src_hw` bounds its frames.  `capacity`: slots per second, default the most boxes any keyframe has.
-    Charades and EPIC verbs: the frame-level pass (get_frame_lfb); EPIC nouns can only be loaded."""
-    if cfg.DATASET in ("charades", "epic"):
-        return get_frame_lfb(params_file, is_train, store, dtype, bank_dtype, capacity, device, n_slots, max_src_hw)
-    from datasets.clip_loader import MinibatchLoader
-    from models.model_builder_video import ModelBuilder
-    from utils import checkpoints
-    from vlfb.engine import Engine
-    if cfg.LFB.LOAD_LFB:
-        return load_lfb(is_train, bank_dtype, device, capacity)
-    assert params_file, "LFB.MODEL_PARAMS_FILE is not specified."
-    split = cfg.TEST.DATA_TYPE or "test"
+def _ava_bank_plan(split, is_train, n, bank_dtype, capacity, device):
+    """-> (the lfb_infer_only AvaIndex, the engine's RoI rows, the empty DeviceBank: a row per video, a step per second up to
+    the last keyframe's, `capacity` slots (default: the most boxes any keyframe has))"""
     index = ava.AvaIndex.from_cfg(split, True, shift=1, get_train_lfb=is_train)
-    most = max(len(index.boxes_and_labels[v][s]) for v, s, _ in index.keyframe_indices)
-    suffix = "_infer_%s" % ("train" if is_train else "test")
-    model = ModelBuilder(train=False, split=split, name="lfb_infer")
-    model.build_model(suffix=suffix, lfb_infer_only=True, shift=1)
-    engine = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED)
-    n = cfg.TEST.BATCH_SIZE // cfg.NUM_GPUS
-    shapes = {"data" + suffix: (n, 3, cfg.TEST.VIDEO_LENGTH, cfg.TEST.CROP_SIZE, cfg.TEST.CROP_SIZE),
-              "labels" + suffix: (n * most, cfg.MODEL.NUM_CLASSES), "proposals" + suffix: (n * most, 5)}
-    engine.plan(collections.OrderedDict((name, shapes[name]) for name in model.input_blob_names))
-    engine.init_params()
-    checkpoints.load_model_from_params_file_for_test(model, params_file)
-    loader = MinibatchLoader(engine, suffix, 0, n_slots=n_slots, max_src_hw=max_src_hw, device=device)
-    frames = store(loader.device, loader.stream)
+    most = passes.most_boxes(index)
     last = max(s for _, s, _ in index.keyframe_indices)
     bank = DeviceBank(index.num_videos, last - ava.AVA_VALID_FRAMES[0] + 1, capacity or most, cfg.LFB.LFB_DIM, bank_dtype,
                       device, step_base=ava.AVA_VALID_FRAMES[0])
-    build_ava_bank(engine, loader, index, frames, bank, rng)
+    return index, n * most, bank
+
+
+def _frame_bank_plan(split, is_train, bank_dtype, device):
+    """-> (the lfb_infer_only CharadesIndex / EpicIndex, the empty DeviceBank: capacity 1, n_steps from the longest video;
+    rows = video indices (Charades) or the videos in the order of the frame lists with their names as `video_ids` (EPIC
+    verbs))"""
+    from datasets import charades, epic
+    sample_freq = frame_sample_freq()
+    if cfg.DATASET == "charades":
+        index = charades.CharadesIndex.from_cfg(split, True, get_train_lfb=is_train)
+        n_videos, video_ids = index.num_videos, None
+        n_steps = max(max(index.num_frames) // sample_freq, 1)
+    else:
+        index = epic.EpicIndex.from_cfg(split, True, shift=1, get_train_lfb=is_train)
+        video_ids = list(index.image_paths)
+        n_videos = len(video_ids)
+        n_steps = max([a[2] for a in index.annotations] + [0]) // sample_freq + 1
+    return index, DeviceBank(n_videos, n_steps, 1, cfg.LFB.LFB_DIM, bank_dtype, device, video_ids=video_ids)
+
+
+def _check_complete(bank, index, is_train):
+    """the reference's completeness conditions of a frame-level bank (construct_lfb, lfb_loader.py:140-152)"""
+    occupied = bank.counts() > 0
+    with_clips = int(occupied.any(axis=1).sum())
+    if cfg.DATASET == "charades":
+        want = cfg.TRAIN.DATASET_SIZE if is_train else cfg.TEST.DATASET_SIZE
+        assert with_clips == want, "the bank holds %d videos, the split has %d" % (with_clips, want)
+    assert with_clips == bank.n_videos, "%d of %d videos have no bank clip" % (bank.n_videos - with_clips, bank.n_videos)
+    assert int(occupied.sum()) == index.get_db_size(), \
+        "%d bank cells are occupied, the pass walked %d clips" % (int(occupied.sum()), index.get_db_size())
+
+
+def get_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capacity=None, device="cuda:0", n_slots=2,
+            max_src_hw=(256, 340), rng=None):
+    """lfb_loader.get_lfb: the bank loaded from LFB.LOAD_LFB_PATH when LFB.LOAD_LFB, else inferred with the baseline
+    parameters `params_file` and written when LFB.WRITE_LFB.  `store(device, stream)` builds the
+    datasets.frame_store.FrameStore (with its `fetch`) on the loader's stream; `max_src_hw` bounds its frames.
+    AVA: the lfb_infer_only engine over every keyframe of the train (is_train) or test LFB box lists (build_ava_bank);
+    `capacity`: slots per second, default the most boxes any keyframe has.
+    Charades and EPIC verbs: the lfb_infer_only basic-head engine (planned without `proposals`) over every bank clip of the
+    train or test frame lists (build_frame_bank), checked for the reference's completeness conditions.  EPIC nouns have no
+    inference pass: that bank can only be loaded."""
+    from utils import checkpoints
+    if cfg.LFB.LOAD_LFB:
+        return load_lfb(is_train, bank_dtype, device, capacity)
+    if cfg.DATASET == "epic" and cfg.EPIC.CLASS_TYPE == "noun":
+        raise NotImplementedError("get_lfb: the EPIC noun bank holds detector features (the reference has no inference pass "
+                                  "for it either); set LFB.LOAD_LFB and LFB.LOAD_LFB_PATH to the detector-built files")
+    assert params_file, "LFB.MODEL_PARAMS_FILE is not specified."
+    frame_level = cfg.DATASET in ("charades", "epic")
+    split = cfg.TEST.DATA_TYPE or "test"
+    n = cfg.TEST.BATCH_SIZE // cfg.NUM_GPUS
+    if frame_level:
+        rows = None
+        index, bank = _frame_bank_plan(split, is_train, bank_dtype, device)
+    else:
+        index, rows, bank = _ava_bank_plan(split, is_train, n, bank_dtype, capacity, device)
+    p = passes.build(store, "_infer_%s" % ("train" if is_train else "test"), dtype, n, cfg.TEST.VIDEO_LENGTH,
+                     cfg.TEST.CROP_SIZE, rows, split=split, name="lfb_infer", lfb_infer_only=True, shift=1, device=device,
+                     n_slots=n_slots, max_src_hw=max_src_hw)
+    p.engine.init_params()
+    checkpoints.load_model_from_params_file_for_test(p.model, params_file)
+    if frame_level:
+        build_frame_bank(p.engine, p.loader, index, p.store, bank, "charades" if cfg.DATASET == "charades" else "epic_verb")
+        _check_complete(bank, index, is_train)
+    else:
+        build_ava_bank(p.engine, p.loader, index, p.store, bank, rng)
     if cfg.LFB.WRITE_LFB:
         write_lfb(bank, is_train)
     return bank
@@ -355,57 +363,6 @@ def get_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capac
 
 def get_frame_lfb(params_file, is_train, store, dtype="bf16", bank_dtype="bf16", capacity=None, device="cuda:0", n_slots=2,
                   max_src_hw=(256, 340)):
-    """get_lfb for cfg.DATASET 'charades' / 'epic': loaded when LFB.LOAD_LFB, else inferred with the lfb_infer_only
-    basic-head engine (planned without `proposals`) over every bank clip of the train (is_train) or test frame lists,
-    checked for the reference's completeness conditions (construct_lfb, lfb_loader.py:140-152) and written when
-    LFB.WRITE_LFB.  Bank geometry: capacity 1, n_steps from the longest video; rows = video indices (Charades) or the videos
-    in the order of the frame lists with their names as `video_ids` (EPIC verbs)."""
-    from datasets import charades, epic
-    from datasets.clip_loader import FrameLoader
-    from models.model_builder_video import ModelBuilder
-    from utils import checkpoints
-    from vlfb.engine import Engine
-    if cfg.LFB.LOAD_LFB:
-        return load_lfb(is_train, bank_dtype, device, capacity)
-    if cfg.DATASET == "epic" and cfg.EPIC.CLASS_TYPE == "noun":
-        raise NotImplementedError("get_lfb: the EPIC noun bank holds detector features (the reference has no inference pass "
-                                  "for it either); set LFB.LOAD_LFB and LFB.LOAD_LFB_PATH to the detector-built files")
-    assert params_file, "LFB.MODEL_PARAMS_FILE is not specified."
-    split = cfg.TEST.DATA_TYPE or "test"
-    sample_freq = frame_sample_freq()
-    if cfg.DATASET == "charades":
-        kind = "charades"
-        index = charades.CharadesIndex.from_cfg(split, True, get_train_lfb=is_train)
-        n_videos, video_ids = index.num_videos, None
-        n_steps = max(max(index.num_frames) // sample_freq, 1)
-    else:
-        kind = "epic_verb"
-        index = epic.EpicIndex.from_cfg(split, True, shift=1, get_train_lfb=is_train)
-        video_ids = list(index.image_paths)
-        n_videos = len(video_ids)
-        n_steps = max([a[2] for a in index.annotations] + [0]) // sample_freq + 1
-    suffix = "_infer_%s" % ("train" if is_train else "test")
-    model = ModelBuilder(train=False, split=split, name="lfb_infer")
-    model.build_model(suffix=suffix, lfb_infer_only=True, shift=1)
-    engine = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED)
-    n = cfg.TEST.BATCH_SIZE // cfg.NUM_GPUS
-    shapes = {"data" + suffix: (n, 3, cfg.TEST.VIDEO_LENGTH, cfg.TEST.CROP_SIZE, cfg.TEST.CROP_SIZE),
-              "labels" + suffix: (n, cfg.MODEL.NUM_CLASSES) if cfg.MODEL.MULTI_LABEL else (n,)}
-    engine.plan(collections.OrderedDict((name, shapes[name]) for name in model.input_blob_names))
-    engine.init_params()
-    checkpoints.load_model_from_params_file_for_test(model, params_file)
-    loader = FrameLoader(engine, suffix, 0, n_slots=n_slots, max_src_hw=max_src_hw, device=device)
-    frames = store(loader.device, loader.stream)
-    bank = DeviceBank(n_videos, n_steps, 1, cfg.LFB.LFB_DIM, bank_dtype, device, video_ids=video_ids)
-    build_frame_bank(engine, loader, index, frames, bank, kind)
-    occupied = bank.counts() > 0
-    with_clips = int(occupied.any(axis=1).sum())
-    if cfg.DATASET == "charades":
-        want = cfg.TRAIN.DATASET_SIZE if is_train else cfg.TEST.DATASET_SIZE
-        assert with_clips == want, "the bank holds %d videos, the split has %d" % (with_clips, want)
-    assert with_clips == n_videos, "%d of %d videos have no bank clip" % (n_videos - with_clips, n_videos)
-    assert int(occupied.sum()) == index.get_db_size(), \
-        "%d bank cells are occupied, the pass walked %d clips" % (int(occupied.sum()), index.get_db_size())
-    if cfg.LFB.WRITE_LFB:
-        write_lfb(bank, is_train)
-    return bank
+    """get_lfb for cfg.DATASET 'charades' / 'epic', under the name it had as a function of its own"""
+    assert cfg.DATASET in ("charades", "epic"), cfg.DATASET
+    return get_lfb(params_file, is_train, store, dtype, bank_dtype, capacity, device, n_slots, max_src_hw)

@@ -71,6 +71,7 @@ class AvaMultiCropTester(object):
 
     def _engine(self, crop, n_clips, frames, n_rois, lfb_shape):
         from models.model_builder_video import ModelBuilder
+        from vlfb import passes
         from vlfb.engine import Engine
         key = (crop, n_clips, frames, n_rois, lfb_shape)
         if key not in self._engines:
@@ -78,17 +79,7 @@ class AvaMultiCropTester(object):
             model = ModelBuilder(train=False, split=cfg.TEST.DATA_TYPE, name="final_test_%d" % crop)
             model.build_model(suffix="_final_test")
             eng = Engine(model, self.dtype, device=self.device)
-            shapes = collections.OrderedDict()
-            for n in model.input_blob_names:
-                if n.startswith("data"):
-                    shapes[n] = (n_clips, 3, frames, crop, crop)
-                elif n.startswith("proposals"):
-                    shapes[n] = (n_rois, 5)
-                elif n.startswith("lfb"):
-                    shapes[n] = lfb_shape
-                elif n.startswith("labels"):
-                    shapes[n] = (n_rois, cfg.MODEL.NUM_CLASSES)
-            eng.plan(shapes)
+            eng.plan(passes.input_shapes(model, "_final_test", n_clips, frames, crop, n_rois, lfb_shape))
             eng.feed_params({k: v for k, v in self.params.items() if k in eng.param_views})
             self._engines[key] = (model, eng)
         return self._engines[key]
@@ -193,7 +184,7 @@ class AvaMultiCropPass(object):
                  rows=None, staging_sets=2, table_rows=None):
         import torch
         from datasets import data_input_helper as dh
-        from vlfb import hip
+        from vlfb import hip, passes
         from vlfb.metrics import DeviceMeter
         assert not index.lfb_infer_only and index.split != "train", "the multi-crop pass walks a test split"
         assert int(staging_sets) >= 2, "at least two staging sets"
@@ -204,8 +195,7 @@ class AvaMultiCropPass(object):
         self.max_crop = int(max_crop)
         self.N = N = index.batch_size // cfg.NUM_GPUS
         self.T = T = int(index.video_length)
-        most = max(len(index.boxes_and_labels[v][s]) for v, s, _ in index.keyframe_indices)
-        self.rows = R = int(rows) if rows is not None else N * most
+        self.rows = R = int(rows) if rows is not None else N * passes.most_boxes(index)
         self.cols = cols = int(cfg.MODEL.NUM_CLASSES)
         self.n_batches = -(-index.get_db_size() // N)
         n_items = int(table_rows) if table_rows is not None else self.n_batches * R

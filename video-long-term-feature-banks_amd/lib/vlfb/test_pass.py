@@ -1,5 +1,6 @@
 """The test driver (reference: tools/test_net.py:48-168): `test_net` dispatches on the dataset, `test_one_crop` runs one
-pass over the Charades / EPIC test split through the frame loader with the metrics accumulated on the device.
+pass (vlfb.passes.run_pass) over the Charades / EPIC test split through the frame loader with the metrics accumulated on
+the device.
 
     meter = test_net(cfg.TEST.PARAMS_FILE, make_store)          # make_store(device, stream) -> FrameStore with its fetch
 
@@ -7,35 +8,16 @@ Charades: CHARADES.NUM_TEST_CLIPS_FINAL_EVAL clips per video (3 shifts x 10 segm
 mAP from the table.  EPIC: the centre crop of every annotated segment; top-1 / top-5 error, and the predictions kept for
 vlfb.epic_eval.evaluate_actions (epic_predictions_<name>.pkl).  AVA: the multi-crop pass (vlfb.multicrop).
 """
-import collections
 import logging
-import time
 
 import numpy as np
 
 from core.config import config as cfg
 from utils import misc
-from vlfb import lfb_pass
+from vlfb import lfb_pass, passes
+from vlfb.passes import Timer           # (test_pass.Timer: the name callers know it by)
 
 logger = logging.getLogger(__name__)
-
-
-class Timer(object):
-    """tic / toc around one iteration.  The loop never waits for the device, so `diff` is the time it took to ENQUEUE the
-    iteration; the device's pace shows in the average, once the loader's slots throttle the loop."""
-
-    def __init__(self):
-        self.total_time, self.calls, self.start_time, self.diff, self.average_time = 0.0, 0, 0.0, 0.0, 0.0
-
-    def tic(self):
-        self.start_time = time.time()
-
-    def toc(self):
-        self.diff = time.time() - self.start_time
-        self.total_time += self.diff
-        self.calls += 1
-        self.average_time = self.total_time / self.calls
-        return self.diff
 
 
 def test_one_crop(params_file, make_store, lfb=None, shift=None, name='final', dtype="bf16", bank_dtype="bf16", device="cuda:0",
@@ -48,13 +30,9 @@ def test_one_crop(params_file, make_store, lfb=None, shift=None, name='final', d
     single-label model) keeps the prediction rows for epic_predictions_<name>.pkl, written into `out_dir`; `name` is
     'final' for these datasets in the reference (get_test_name, test_net.py:171-181).
     -> the utils.metrics.MetricsCalculator"""
-    import torch
     import utils.metrics as metrics
     from datasets import charades, epic
-    from datasets.clip_loader import FrameLoader
-    from models.model_builder_video import ModelBuilder
     from utils import checkpoints
-    from vlfb.engine import Engine
     assert cfg.DATASET in ('charades', 'epic'), "test_one_crop: the frame-level datasets (AVA: vlfb.multicrop)"
     assert params_file, 'No params files specified for testing model.'
     np.random.seed(cfg.RNG_SEED)
@@ -65,49 +43,25 @@ def test_one_crop(params_file, make_store, lfb=None, shift=None, name='final', d
     split = cfg.TEST.DATA_TYPE or "test"
     if shift is None:
         shift = cfg.TEST.CROP_SHIFT
-    bank_video = None
     if cfg.DATASET == 'charades':
-        index, bank_kind = charades.CharadesIndex.from_cfg(split, False), "charades"
+        index = charades.CharadesIndex.from_cfg(split, False)
     else:
         index = epic.EpicIndex.from_cfg(split, False, shift=shift)
-        bank_kind = "epic_noun" if cfg.EPIC.CLASS_TYPE == 'noun' else "epic_verb"
-        if bank_kind == "epic_noun":                      # the noun bank is keyed by video index, the verb bank by name
-            bank_video = index.video_name_to_idx.__getitem__
     suffix = '_final_test'
-    model = ModelBuilder(train=False, split=split, name="test")
-    model.build_model(suffix=suffix, lfb=lfb, shift=shift)
-    engine = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED)
-    n = cfg.TEST.BATCH_SIZE // cfg.NUM_GPUS
-    shapes = {"data" + suffix: (n, 3, cfg.TEST.VIDEO_LENGTH, cfg.TEST.CROP_SIZE, cfg.TEST.CROP_SIZE),
-              "labels" + suffix: (n, cfg.MODEL.NUM_CLASSES) if cfg.MODEL.MULTI_LABEL else (n,),
-              "lfb" + suffix: (n, cfg.LFB.WINDOW_SIZE, cfg.LFB.LFB_DIM)}
-    engine.plan(collections.OrderedDict((blob, shapes[blob]) for blob in model.input_blob_names))
-    uses_bank = ("lfb" + suffix) in model.input_blob_names
-    assert not uses_bank or lfb is not None, "the model reads a feature bank (LFB.ENABLED): no bank was given or built"
+    p = passes.build(make_store, suffix, dtype, cfg.TEST.BATCH_SIZE // cfg.NUM_GPUS, cfg.TEST.VIDEO_LENGTH, cfg.TEST.CROP_SIZE,
+                     split=split, name="test", bank=lfb, shift=shift, device=device, n_slots=n_slots, max_src_hw=max_src_hw)
     total_test_net_iters = misc.get_total_test_iters(index)
-    loader = FrameLoader(engine, suffix, 0, n_slots=n_slots, max_src_hw=max_src_hw, bank=lfb if uses_bank else None,
-                         bank_kind=bank_kind if uses_bank else None, device=device)
-    store = make_store(loader.device, loader.stream)
     keep = (not cfg.MODEL.MULTI_LABEL) if keep_predictions is None else bool(keep_predictions)
-    test_meter = metrics.MetricsCalculator(engine, split, video_idx_to_name=index.video_idx_to_name, keep_predictions=keep)
-    engine.init_params()
-    checkpoints.load_model_from_params_file_for_test(model, params_file)
+    test_meter = metrics.MetricsCalculator(p.engine, split, video_idx_to_name=index.video_idx_to_name, keep_predictions=keep)
+    p.engine.init_params()
+    checkpoints.load_model_from_params_file_for_test(p.model, params_file)
     timer = Timer()
-    loader.start(lfb_pass.frame_minibatch_source(index, store, bank_video))
-    test_iter = -1
-    try:
-        for test_iter in range(total_test_net_iters):
-            timer.tic()
-            loader.deliver(loader.next())
-            engine.forward()
-            timer.toc()
-            test_meter.calculate_and_log_all_metrics_test(test_iter, timer, total_test_net_iters, suffix)
-    finally:
-        loader.stop()
-    torch.cuda.current_stream().synchronize()
-    store.check_decoded()
+    ran = passes.run_pass(
+        p.engine, p.loader, p.store, lfb_pass.frame_minibatch_source(index, p.store, passes.bank_video(index)),
+        total_test_net_iters, timer,
+        lambda it, mb: test_meter.calculate_and_log_all_metrics_test(it, timer, total_test_net_iters, suffix))
     test_meter.finalize_metrics(name=name, out_dir=out_dir)
-    test_meter.log_final_metrics(test_iter, total_test_net_iters)
+    test_meter.log_final_metrics(ran - 1, total_test_net_iters)
     return test_meter
 
 

@@ -16,24 +16,12 @@ import numpy as np
 
 from core.config import config as cfg
 from utils import misc
-from vlfb import lfb_pass
-from vlfb.test_pass import Timer
+from vlfb import lfb_pass, passes
+from vlfb.passes import Timer
 
 logger = logging.getLogger(__name__)
 
 Wrapper = collections.namedtuple("Wrapper", "model engine index loader store timer meter suffix bank_video")
-
-
-def _bank_kind():
-    if cfg.DATASET == 'charades':
-        return "charades"
-    return "epic_noun" if cfg.EPIC.CLASS_TYPE == 'noun' else "epic_verb"
-
-
-def _ava_rows(index, n):
-    """RoI rows of a plan: clips per GPU x the most boxes any keyframe of the index has"""
-    most = max(len(index.boxes_and_labels[v][s]) for v, s, _ in index.keyframe_indices)
-    return n * most
 
 
 def create_wrapper(is_train, make_store, lfb, owner=None, dtype="mix", device="cuda:0", n_slots=2, max_src_hw=(256, 340),
@@ -43,47 +31,24 @@ def create_wrapper(is_train, make_store, lfb, owner=None, dtype="mix", device="c
     MetricsCalculator.  `owner`: the engine whose parameters this one aliases (the train engine, for the test wrapper and
     the precise-BN aux engine).  -> Wrapper"""
     from datasets import ava, charades, epic
-    from datasets.clip_loader import FrameLoader, MinibatchLoader
-    from models.model_builder_video import ModelBuilder
-    from vlfb.engine import Engine
     import utils.metrics as metrics
     if is_train:
         suffix, split, part = suffix or '_train', cfg.TRAIN.DATA_TYPE, cfg.TRAIN
     else:
         suffix, split, part = suffix or '_test', cfg.TEST.DATA_TYPE, cfg.TEST
-    model = ModelBuilder(train=is_train, split=split, name=split, force_fw_only=force_fw_only)
-    model.build_model(suffix=suffix, lfb=lfb)
-    engine = Engine(model, dtype, device=device, base_seed=cfg.RNG_SEED, share_params_with=owner)
     n = part.BATCH_SIZE // cfg.NUM_GPUS
-    bank_video = None
+    rows = None
     if cfg.DATASET == 'ava':
         index = ava.AvaIndex.from_cfg(split, False)
-        rows = _ava_rows(index, n)
-        k = cfg.LFB.WINDOW_SIZE * cfg.AVA.LFB_MAX_NUM_FEAT_PER_STEP
-        shapes = {"data" + suffix: (n, 3, part.VIDEO_LENGTH, part.CROP_SIZE, part.CROP_SIZE),
-                  "labels" + suffix: (rows, cfg.MODEL.NUM_CLASSES), "proposals" + suffix: (rows, 5),
-                  "lfb" + suffix: (rows, k, cfg.LFB.LFB_DIM)}
+        rows = n * passes.most_boxes(index)
+    elif cfg.DATASET == 'charades':
+        index = charades.CharadesIndex.from_cfg(split, False)
     else:
-        if cfg.DATASET == 'charades':
-            index = charades.CharadesIndex.from_cfg(split, False)
-        else:
-            index = epic.EpicIndex.from_cfg(split, False, shift=None if is_train else cfg.TEST.CROP_SHIFT)
-            if _bank_kind() == "epic_noun":              # the noun bank is keyed by video index, the verb bank by name
-                bank_video = index.video_name_to_idx.__getitem__
-        shapes = {"data" + suffix: (n, 3, part.VIDEO_LENGTH, part.CROP_SIZE, part.CROP_SIZE),
-                  "labels" + suffix: (n, cfg.MODEL.NUM_CLASSES) if cfg.MODEL.MULTI_LABEL else (n,),
-                  "lfb" + suffix: (n, cfg.LFB.WINDOW_SIZE, cfg.LFB.LFB_DIM)}
-    engine.plan(collections.OrderedDict((blob, shapes[blob]) for blob in model.input_blob_names))
-    uses_bank = ("lfb" + suffix) in model.input_blob_names
-    assert not uses_bank or lfb is not None, "the model reads a feature bank (LFB.ENABLED): no bank was given"
-    aug = 1 if (is_train and split == "train") else 0
-    if cfg.DATASET == 'ava':
-        loader = MinibatchLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=lfb if uses_bank else None,
-                                 device=device)
-    else:
-        loader = FrameLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=lfb if uses_bank else None,
-                             bank_kind=_bank_kind() if uses_bank else None, device=device)
-    store = make_store(loader.device, loader.stream)
+        index = epic.EpicIndex.from_cfg(split, False, shift=None if is_train else cfg.TEST.CROP_SHIFT)
+    model, engine, loader, store = passes.build(
+        make_store, suffix, dtype, n, part.VIDEO_LENGTH, part.CROP_SIZE, rows, train=is_train, split=split, name=split,
+        force_fw_only=force_fw_only, bank=lfb, aug=1 if (is_train and split == "train") else 0, owner=owner, device=device,
+        n_slots=n_slots, max_src_hw=max_src_hw)
     meter = None
     if not force_fw_only:
         scored = cfg.DATASET == 'ava' and not is_train
@@ -91,8 +56,8 @@ def create_wrapper(is_train, make_store, lfb, owner=None, dtype="mix", device="c
             engine, split, video_idx_to_name=index.video_idx_to_name,
             ava_groundtruth=ava_groundtruth if scored else None, excluded_keys=excluded_keys if scored else None,
             class_whitelist=class_whitelist if scored else None, categories=categories if scored else None,
-            ava_table_rows=(misc.get_total_test_iters(index) * shapes["labels" + suffix][0]) if scored else None)
-    return Wrapper(model, engine, index, loader, store, Timer(), meter, suffix, bank_video)
+            ava_table_rows=(misc.get_total_test_iters(index) * rows) if scored else None)
+    return Wrapper(model, engine, index, loader, store, Timer(), meter, suffix, passes.bank_video(index))
 
 
 def train_source(w, rng, aug_rng):
@@ -110,12 +75,11 @@ def eval_pass(test, name='latest', curr_iter=None, rng=None):
     EPIC: the loop of test_one_crop; nothing is loaded and no predictions are kept.  AVA: the single-crop pass -- the
     test AvaIndex (built under AVA.FULL_EVAL = FULL_EVAL_DURING_TRAINING, DETECTION_SCORE_THRESH = _TRAIN), centre crop,
     add_ava_batch(metadata, original_boxes) per iteration.  -> iterations run"""
-    import torch
     from datasets import ava
     from vlfb import dist
     if dist.world_size() > 1:
         raise NotImplementedError("eval_pass: the in-training evaluation is single-process (world size %d)" % dist.world_size())
-    meter, loader, engine = test.meter, test.loader, test.engine
+    meter, loader = test.meter, test.loader
     meter.reset()
     logger.info("=> Testing model")
     total = misc.get_total_test_iters(test.index)
@@ -125,29 +89,19 @@ def eval_pass(test, name='latest', curr_iter=None, rng=None):
                                       bank=loader.bank)
     else:
         source = lfb_pass.frame_minibatch_source(test.index, test.store, test.bank_video)
-    loader.start(source)
-    test_iter = -1
-    try:
-        for test_iter in range(total):
-            test.timer.tic()
-            mb = loader.next()
-            loader.deliver(mb)
-            engine.forward()
-            test.timer.toc()
-            if cfg.DATASET == 'ava' and meter.meter is not None:
-                meter.add_ava_batch(mb.metadata[:, :2], mb.original_boxes)
-            meter.calculate_and_log_all_metrics_test(test_iter, test.timer, total, test.suffix)
-    finally:
-        loader.stop()
-    torch.cuda.current_stream().synchronize()
-    test.store.check_decoded()
+
+    def score(it, mb):
+        if cfg.DATASET == 'ava' and meter.meter is not None:
+            meter.add_ava_batch(mb.metadata[:, :2], mb.original_boxes)
+        meter.calculate_and_log_all_metrics_test(it, test.timer, total, test.suffix)
+    ran = passes.run_pass(test.engine, loader, test.store, source, total, test.timer, score)
     if cfg.DATASET == 'ava' and meter.ava_groundtruth is None:
         meter.full_map = 0.0                             # (no annotation files were given: nothing to score against)
     else:
         meter.finalize_metrics(name=name)
     meter.compute_and_log_best()
-    meter.log_final_metrics(curr_iter if curr_iter is not None else test_iter, None if curr_iter is not None else total)
-    return test_iter + 1
+    meter.log_final_metrics(curr_iter if curr_iter is not None else ran - 1, None if curr_iter is not None else total)
+    return ran
 
 
 def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groundtruth=None, excluded_keys=(),
@@ -205,13 +159,8 @@ def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groun
             from vlfb.precise_bn import PreciseBN
 
             def make_loader(engine, suffix):
-                from datasets.clip_loader import FrameLoader, MinibatchLoader
-                aug = 1 if cfg.TRAIN.DATA_TYPE == "train" else 0
-                if cfg.DATASET == 'ava':
-                    loader = MinibatchLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=tr.loader.bank, device=device)
-                else:
-                    loader = FrameLoader(engine, suffix, aug, n_slots=n_slots, max_src_hw=max_src_hw, bank=tr.loader.bank,
-                                         bank_kind=tr.loader.bank_kind, device=device)
+                loader = passes.make_loader(engine, suffix, 1 if cfg.TRAIN.DATA_TYPE == "train" else 0, tr.loader.bank, n_slots,
+                                            max_src_hw, device)
                 w = tr._replace(loader=loader, store=make_store(loader.device, loader.stream))
                 aux.append(w)
                 # its own walk over the training split, as the reference's bn_aux model has its own data loader
