@@ -194,7 +194,8 @@ typedef struct vlfb_conv_desc {
    *             the fp16 backward of the "mix" path reads (positive values stay positive in the copy) */
   int32_t a_planes, p_planes, o_planes;
   int32_t wgrad_bias; /* WGRAD only: 1 = the launch also produces the bias gradient db[p] = alpha * rowscale[p] * sum_m P[m][p]
-                         (vlfb_conv_run_wgrad_bias); counted in vlfb_conv_workspace_bytes */
+                         (vlfb_conv_run_wgrad_bias; a batched launch sums over its batch elements too: db stays [Cn]);
+                         counted in vlfb_conv_workspace_bytes */
   int64_t a_pstride, p_pstride, o_pstride;
 } vlfb_conv_desc;
 

@@ -2,12 +2,14 @@
 what a descriptor means.
 
 `Case(desc, ops)` allocates random operands in the layout the descriptor implies (seeded, values in a chosen range), every
-device buffer with slack past its extent so that a sizing mistake here reads padding instead of faulting the card, and
+device input with slack past its extent so that a sizing mistake here reads padding instead of faulting the card, and
 computes the expected outputs in float64 on the CPU.  `ops` names the optional operands of the launch ("bias", "R", "R_lo",
 "mask", "rowscale", "O_lo", "O_planes", "dbias", "class0_inplace").  `Case.run()` launches the descriptor through
 vlfb_conv_run and `Case.check()` compares every output with the model:
   * every output element the launch must write is NaN before the launch and must be finite after it;
   * every element around and between the rows of an output (guard bands, ldo > Cn gaps) holds a sentinel that must survive;
+  * the workspace is exactly the vlfb_conv_workspace_bytes of the descriptor, NaN-filled, between two sentinel bands that
+    must survive: a slab write past the stated size shows in the bands, a slab element read but never written in the output;
   * relative L2 at the bars of the kernel tests, and an elementwise bound
         |got - ref| <= c * (u_prod + u_acc(K)) * |alpha| (|A|.|B|)  +  u_out * (|alpha| |A|.|B| + |bias| + |R|)
     tight enough that one dropped 32-wide k-tile of one output tile fails it.
@@ -403,7 +405,8 @@ class Case:
                 self.dbias_ref = alpha * ps.sum(1).sum(0) * rs
                 self.dbias_mag = abs(alpha) * ps.abs().sum(1).sum(0) * (rs.abs() if self.rowscale is not None else 1.0)
             if d["accumulate"]:
-                self.o_init = self._rand(B, rows, cols).float().double()
+                # (the launch reads the earlier O from memory: values of the output type, not fp32 ones rounded on upload)
+                self.o_init = self._rand(B, rows, cols).to(TDT[d["out_dtype"]]).double()
                 v = v + self.o_init
                 extra = extra + self.o_init.abs()
         else:
@@ -555,8 +558,17 @@ class Case:
             self.dbias[GUARD:GUARD + d["Cn"]] = float("nan")
             self.dbias = self.dbias.to(dev)
             kw["dbias"] = self.dbias[GUARD:]
+        # the workspace: exactly vlfb_conv_workspace_bytes between two sentinel bands, NaN where the launch may write (a slab
+        # element a reduce reads without any workgroup having written it turns the output NaN)
         ws_bytes = hip.conv_workspace_bytes(desc)
-        ws = torch.empty(ws_bytes // 4 + SLACK, dtype=torch.float32, device=dev) if ws_bytes else None
+        self.ws = ws = None
+        if ws_bytes:
+            assert ws_bytes % 4 == 0, ws_bytes
+            self.ws = torch.full((GUARD + ws_bytes // 4 + GUARD,), SENTINEL, dtype=torch.float32)
+            self.ws[GUARD:-GUARD] = float("nan")
+            self.ws = self.ws.to(dev)
+            ws = self.ws[GUARD:-GUARD]
+            assert ws.numel() * ws.element_size() == ws_bytes
         A = self.A_dev.to(dev)
         Bop = self.B_dev.to(dev) if d["mode"] != WGRAD else None
         P = self.P_dev.to(dev) if d["mode"] == WGRAD else None
@@ -577,6 +589,11 @@ class Case:
         """compare every output of the launch with the model; returns a dict of the worst figures (raises AssertionError)"""
         d = self.d
         out = {}
+        if self.ws is not None:
+            w = self.ws.cpu().double()
+            live = torch.zeros(w.numel(), dtype=torch.bool)
+            live[GUARD:-GUARD] = True
+            self._guard("workspace", w, live)
         O = self.O.cpu().double()
         self._guard("O", O, self.o_live)
         got = self._live_values(O, self.o_live)

@@ -721,13 +721,15 @@ __global__ __launch_bounds__(CL * G) void wgrad_reduce_kernel(const float* ws, c
 }
 
 // bias-gradient partial rows of a split WGRAD (GP::dbias): ws_b[split][n] -> out[n], splits folded in order
+// (add: out[n] += ..., the further batch elements of a batched launch)
 __global__ void wgrad_bias_reduce_kernel(const float* __restrict__ ws_b, float* __restrict__ out,
-                                         const float* __restrict__ rowscale, int n, int splits, float alpha) {
+                                         const float* __restrict__ rowscale, int n, int splits, float alpha, int add) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float s = 0.f;
   for (int k = 0; k < splits; ++k) s += ws_b[(long long)k * n + i];
-  out[i] = s * alpha * (rowscale ? rowscale[i] : 1.f);
+  const float v = s * alpha * (rowscale ? rowscale[i] : 1.f);
+  out[i] = add ? out[i] + v : v;
 }
 
 // ---- host side: the launch of a plan (the planner is vlfb_conv_plan.hip) -------------------------
@@ -1040,10 +1042,16 @@ static int conv_run_impl(const vlfb_conv_desc* d, const void* A, const void* B, 
     VLFB_REQUIRE(!d->a_planes, "conv: wgrad_bias with pre-split operands is not supported (pass the fp32 operands)");
     const int slabs = colsum_slabs(d->dtype, g.M, d->Cn);
     float* part = g.ws + (pl.splits > 1 ? (long long)pl.splits * ((long long)d->Cn * g.ldo) : 0);
-    rc = colsum_partials(P, d->dtype, g.M, d->Cn, g.ldp, part, s);
-    if (rc != VLFB_OK) return rc;
-    hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((d->Cn + 63) / 64)), dim3(64), 0, s, part, dbias, rowscale,
-                       d->Cn, slabs, d->alpha);
+    // (a batched launch: db sums over the batch elements as well -- one pass per element through the same partial rows,
+    // added in batch order on the stream)
+    const int batch = d->batch > 0 ? d->batch : 1;
+    const long long p_es = d->dtype == VLFB_F32 ? 4 : 2;
+    for (int z = 0; z < batch; ++z) {
+      rc = colsum_partials((const char*)P + (long long)z * g.p_bs * p_es, d->dtype, g.M, d->Cn, g.ldp, part, s);
+      if (rc != VLFB_OK) return rc;
+      hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((d->Cn + 63) / 64)), dim3(64), 0, s, part, dbias, rowscale,
+                         d->Cn, slabs, d->alpha, z > 0 ? 1 : 0);
+    }
   }
   // (a launch with fused column sums and splits: its bias partial rows are folded by the weight reduce below)
   const float* bias_rows = (dbias && pl.bias_fused && pl.splits > 1) ? g.ws + (long long)pl.splits * ((long long)d->Cn * g.ldo) : nullptr;
