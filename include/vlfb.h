@@ -1056,6 +1056,21 @@ int vlfb_multicrop_merge(const void* logits, int dtype, int64_t shift_stride, in
                          const int32_t* frame_hw, int64_t rows, int64_t cols, int scale, int max_crop, int flip, int first,
                          double* acc, float* out32, uint8_t* valid, vlfb_stream_t stream);
 
+/* Rank interleave: the global stream order of a data-parallel pass rebuilt from the ranks' own row tables.  Rank p of `world`
+ * issued slices p, p + world, p + 2 * world, ... of the single-process walk, `b` rows each, and kept them in that order in
+ * parts[p] (DEVICE address, part_rows[p] rows of row_bytes bytes; `parts` and `part_rows` themselves are HOST arrays of
+ * `world` entries).  Destination row g, 0 <= g < total, becomes row (g / (b * world)) * b + g % b of part (g / b) % world:
+ * per global iteration, rank 0 .. world-1, which is the order the reference's get_multi_gpu_outputs sees the rows in.
+ * Destination rows at or after `total` are not touched.  A pure copy of bytes: every destination byte has one writer, no
+ * atomics, no dependence on launch order.  16-byte accesses when row_bytes, dst and every part that is read allow them,
+ * else 4-byte accesses, else bytes.
+ * VLFB_ERR_ARG before anything is launched: world outside 1..VLFB_ROWS_INTERLEAVE_MAX_WORLD, b < 1, row_bytes < 1,
+ * total < 0, a NULL parts / part_rows, a NULL dst with total > 0, a part that is shorter than the last row asked of it
+ * (or NULL while rows are asked of it).  total == 0 succeeds and launches nothing. */
+#define VLFB_ROWS_INTERLEAVE_MAX_WORLD 64
+int vlfb_rows_interleave(const void* const* parts, const int64_t* part_rows, int world, int64_t b, int64_t row_bytes,
+                         int64_t total, void* dst, vlfb_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

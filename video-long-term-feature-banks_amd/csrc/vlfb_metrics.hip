@@ -739,3 +739,59 @@ extern "C" int vlfb_multicrop_merge(const void* logits, int dtype, int64_t shift
   else with_elem(dtype, launch);
   return check_launch("multicrop_merge");
 }
+
+// ---- rank interleave: the global stream order of a pass rebuilt from the ranks' own row tables -------------------------
+// A pure row copy (row_copy of csrc/vlfb_lfb.hip without the conversion): a wave per destination row, every destination
+// byte has one writer, no atomics.  V is the widest access the host found legal for `row_bytes` and every base address.
+namespace vlfb {
+
+constexpr int IL_THREADS = 256, IL_MAX_BLOCKS = 65536;
+struct InterleaveParts { const char* part[VLFB_ROWS_INTERLEAVE_MAX_WORLD]; };
+
+template <typename V>
+__global__ __launch_bounds__(IL_THREADS) void rows_interleave_kernel(InterleaveParts parts, int world, long long b, long long row_bytes,
+                                                                     long long total, char* __restrict__ dst) {
+  const int lane = threadIdx.x & 63, waves = IL_THREADS / 64;
+  const long long per = row_bytes / (long long)sizeof(V);
+  for (long long g = (long long)blockIdx.x * waves + (threadIdx.x >> 6); g < total; g += (long long)gridDim.x * waves) {
+    const long long slice = g / b;
+    const long long src_row = (slice / world) * b + g % b;
+    const V* s = reinterpret_cast<const V*>(parts.part[slice % world] + src_row * row_bytes);
+    V* d = reinterpret_cast<V*>(dst + g * row_bytes);
+    for (long long i = lane; i < per; i += 64) d[i] = s[i];
+  }
+}
+
+}  // namespace vlfb
+
+extern "C" int vlfb_rows_interleave(const void* const* parts, const int64_t* part_rows, int world, int64_t b, int64_t row_bytes,
+                                    int64_t total, void* dst, vlfb_stream_t stream) {
+  VLFB_REQUIRE(world >= 1 && world <= VLFB_ROWS_INTERLEAVE_MAX_WORLD, "rows_interleave: world = %d outside 1..%d", world,
+               VLFB_ROWS_INTERLEAVE_MAX_WORLD);
+  VLFB_REQUIRE(b >= 1 && b < (1ll << 31), "rows_interleave: slice height b = %lld outside 1..2^31-1", (long long)b);
+  VLFB_REQUIRE(row_bytes >= 1 && row_bytes < (1ll << 31), "rows_interleave: row_bytes = %lld outside 1..2^31-1", (long long)row_bytes);
+  VLFB_REQUIRE(total >= 0 && total < (1ll << 40), "rows_interleave: total = %lld outside 0..2^40-1", (long long)total);
+  VLFB_REQUIRE(parts != nullptr && part_rows != nullptr, "rows_interleave: parts and part_rows are required");
+  if (total == 0) return VLFB_OK;
+  VLFB_REQUIRE(dst != nullptr, "rows_interleave: dst is required");
+  // part p is asked for b rows per complete global iteration, and for its share of the last, cut one
+  const long long per_iter = (long long)b * world, full = total / per_iter, rem = total % per_iter;
+  InterleaveParts ip;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(dst) | (uintptr_t)row_bytes;
+  for (int p = 0; p < VLFB_ROWS_INTERLEAVE_MAX_WORLD; ++p) ip.part[p] = nullptr;
+  for (int p = 0; p < world; ++p) {
+    const long long need = full * b + std::min<long long>(std::max<long long>(rem - (long long)p * b, 0), b);
+    VLFB_REQUIRE(part_rows[p] >= need, "rows_interleave: part %d holds %lld rows, %lld are asked of it", p, (long long)part_rows[p], need);
+    VLFB_REQUIRE(need == 0 || parts[p] != nullptr, "rows_interleave: part %d is NULL, %lld rows are asked of it", p, need);
+    ip.part[p] = static_cast<const char*>(parts[p]);
+    if (need) bits |= reinterpret_cast<uintptr_t>(parts[p]);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long blocks = (total + IL_THREADS / 64 - 1) / (IL_THREADS / 64);
+  const unsigned grid = (unsigned)std::min<long long>(blocks, IL_MAX_BLOCKS);
+  char* d = static_cast<char*>(dst);
+  if ((bits & 15) == 0) rows_interleave_kernel<uint4><<<grid, IL_THREADS, 0, s>>>(ip, world, b, row_bytes, total, d);
+  else if ((bits & 3) == 0) rows_interleave_kernel<uint32_t><<<grid, IL_THREADS, 0, s>>>(ip, world, b, row_bytes, total, d);
+  else rows_interleave_kernel<uint8_t><<<grid, IL_THREADS, 0, s>>>(ip, world, b, row_bytes, total, d);
+  return check_launch("rows_interleave");
+}

@@ -162,13 +162,18 @@ class AvaIndex(object):
         return out
 
 
-def minibatch_source(index, store, rng, iterations=None, bank=None):
+def minibatch_source(index, store, rng, iterations=None, bank=None, aug_rng=None):
     """generator of what MinibatchLoader.start takes: (frames_list, boxes_list, labels_list, meta, rng, spatial_shift_pos)
     with clips as (store, video, frame_numbers) into the FrameStore `store` (decode stays the caller's, through
     store.fetch), boxes as (k, 4) normalised arrays, labels as (k, classes) int32 arrays and
     meta = dict(iteration=, videos=, secs=, padded=[bool per clip]) (+ lfb_slots per clip with `bank`, whose counts are read
     once).  Outside train: one pass over 0 .. db_size in order, in batches, the last one padded.  In train: passes without
-    end (or `iterations` minibatches), the indices shuffled with `rng` at the start of every pass."""
+    end (or `iterations` minibatches), the indices shuffled with `rng` at the start of every pass.
+    aug_rng: the generator yielded to the loader for its augmentation draws, default `rng` itself (the reference's one
+    np.random).  With its own, the walk -- the shuffles and get_minibatch_info's draws -- is `rng`'s alone, whatever thread
+    consumes what is yielded: the ranks of a job seed it alike and walk alike (vlfb.lfb_pass.rank_source)."""
+    if aug_rng is None:
+        aug_rng = rng
     n = index.batch_size // cfg.NUM_GPUS
     size = index.get_db_size()
     counts = bank.counts() if bank is not None else None
@@ -190,7 +195,7 @@ def minibatch_source(index, store, rng, iterations=None, bank=None):
             shift = infos[0].shift if infos[0].shift is not None else CENTER_CROP_INDEX
             yield ([(store, c.video, c.seq) for c in infos],
                    [np.asarray(c.boxes, dtype=np.float64).reshape(-1, 4) for c in infos],
-                   [np.stack([construct_label_array(l) for l in c.labels]) for c in infos], meta, rng, shift)
+                   [np.stack([construct_label_array(l) for l in c.labels]) for c in infos], meta, aug_rng, shift)
             it += 1
         if index.split != "train":
             return

@@ -95,8 +95,10 @@ class MetricsCalculator(object):
                  excluded_keys=None, class_whitelist=None, categories=None, ava_table_rows=None, keep_predictions=False):
         """keep_predictions: on a single-label test split the meter also keeps the first TEST.DATASET_SIZE prediction rows
         and labels on the device (vlfb_topk_hits_keep) and finalize_metrics writes them as epic_predictions_<name>.pkl
-        (metrics.py:222-226), the input of vlfb.epic_eval.evaluate_actions.  With more than one rank this raises
-        NotImplementedError: the reference's gather order of a multi-GPU test is not reproduced.
+        (metrics.py:222-226), the input of vlfb.epic_eval.evaluate_actions.
+        Under a process group of N ranks every rank keeps only the rows it issued (the slices of vlfb.lfb_pass.rank_source),
+        in tables sized for its ceil(P / N) of the P slices; finalize_metrics gathers them, rebuilds the single-process
+        stream order (vlfb.metrics.interleave_rows) and scores that with the single-process kernels.
         ava_groundtruth: read_csv's (boxes, labels, scores) -- with it an AVA config is scored (frame-mAP);
         excluded_keys / class_whitelist / categories: read_exclusions' and read_labelmap's results; ava_table_rows: rows of
         the score table (default: every row ceil(TEST.DATASET_SIZE / TEST.BATCH_SIZE) iterations issue, padding included)"""
@@ -118,31 +120,46 @@ class MetricsCalculator(object):
         self.class_whitelist = set(class_whitelist) if class_whitelist else None
         self.categories = categories
         self.keep_predictions = bool(keep_predictions) and not cfg.MODEL.MULTI_LABEL and split != 'train'
-        if self.keep_predictions and dist.world_size() > 1:
-            raise NotImplementedError("keep_predictions: the kept prediction table is single-process only (world size %d)"
-                                      % dist.world_size())
+        self.world = dist.world_size()
         from vlfb.engine import LossStep
         heads = [st for st in engine.steps if isinstance(st, LossStep) and st.prob is not None]
         if cfg.DATASET == 'ava' and ava_groundtruth is not None and heads and split != 'train':
             cols, self.batch_rows = heads[0].cols, heads[0].rows
             if ava_table_rows is None:
-                per_rank = max(cfg.TEST.BATCH_SIZE // dist.world_size(), 1)
-                ava_table_rows = -(-max(cfg.TEST.DATASET_SIZE // dist.world_size(), 1) // per_rank) * self.batch_rows
+                ava_table_rows = self._rank_slices(cfg.TEST.DATASET_SIZE, max(cfg.TEST.BATCH_SIZE // self.world, 1)) * self.batch_rows
             self.meter = DeviceMeter("ava", cols, n_items=int(ava_table_rows), device=engine.device)
             engine.attach_meter(self.meter, labels=test_labels)
         if cfg.DATASET != 'ava' and heads:
             cols, self.batch_rows = heads[0].cols, heads[0].rows
             if cfg.MODEL.MULTI_LABEL:
                 if split != 'train':                 # (the reference computes no mAP while training: full_map = 0)
-                    total = self.num_test_clips * cfg.TEST.DATASET_SIZE // dist.world_size()
-                    self.meter = DeviceMeter("map", cols, n_items=max(total // self.num_test_clips, 1), total_rows=total,
-                                             device=engine.device)
+                    total = self.num_test_clips * cfg.TEST.DATASET_SIZE
+                    self._map_items, self._map_total = max(total // self.num_test_clips, 1), total
+                    if self.world > 1:               # this rank's rows with their labels, merged in finalize_metrics
+                        self.meter = DeviceMeter("ava", cols, n_items=self._rank_slices(total, self.batch_rows) * self.batch_rows,
+                                                 device=engine.device, keep_labels=True)
+                    else:
+                        self.meter = DeviceMeter("map", cols, n_items=self._map_items, total_rows=total, device=engine.device)
             else:
                 keep = int(cfg.TEST.DATASET_SIZE) if self.keep_predictions else None
+                if keep is not None and self.world > 1:
+                    keep = self._rank_slices(keep, self.batch_rows) * self.batch_rows
                 self.meter = DeviceMeter("topk", cols, ks=(1, 5), device=engine.device, keep_rows=keep)
             if self.meter is not None:
                 engine.attach_meter(self.meter, labels=test_labels)
         self.reset()
+
+    def _rank_slices(self, db_size, n):
+        """slices of `n` a rank runs of a pass over `db_size`: ceil(P / world) of the P = ceil(db_size / n)"""
+        return -(-(-(-int(db_size) // int(n))) // self.world)
+
+    def _gather_parts(self, *tensors):
+        """the rows this rank issued (its cursor) of each 2-D device tensor, from every rank: dist.gather_ragged moves bytes,
+        exact on gloo and nccl.  -> one list of per-rank tensors for each of `tensors`"""
+        rows = dist.gather_objects(self.meter.counters()[2])
+        for t in tensors:
+            assert max(rows) <= t.shape[0], "%d rows were issued into a table of %d" % (max(rows), t.shape[0])
+        return [dist.gather_ragged(t, rows) for t in tensors]
 
     def reset(self):
         logger.info('Resetting {} metrics...'.format(self.split))
@@ -210,7 +227,8 @@ class MetricsCalculator(object):
         if not cfg.MODEL.MULTI_LABEL and self.meter is not None:
             cur_err, cur_err5, _, _ = self._read_topk()
             log_str += ' top1 {:7.3f} top5 {:7.3f}'.format(cur_err, cur_err5)
-        print(log_str)
+        if dist.rank() == 0:
+            print(log_str)
 
     def calculate_and_log_all_metrics_test(self, curr_iter, timer, total_iters, suffix=''):
         cur_batch_size = self.batch_rows * dist.world_size() if self.meter is not None else 0
@@ -227,7 +245,8 @@ class MetricsCalculator(object):
                 ' current batch {}',
                 ' aggregated batch {}',
             )).format(curr_iter + 1, total_iters, timer.diff, cur_batch_size, self.aggr_batch_size)
-            print(test_str + tail)
+            if dist.rank() == 0:
+                print(test_str + tail)
 
     def finalize_metrics(self, is_train=False, name='latest', out_dir=None):
         """the final figures: mAP of the merged table (Charades), or the aggregated top-1 / top-5 error.  A calculator
@@ -247,18 +266,13 @@ class MetricsCalculator(object):
             rows = np.concatenate(self._ava_rows) if self._ava_rows else np.zeros(0, np.int64)
             boxes = np.concatenate(self._ava_boxes) if self._ava_boxes else np.zeros((0, 4))
             keys = list(self._ava_keys)
-            if dist.world_size() > 1:
-                # every rank holds the rows it tested: gather the tables once, shift every rank's row numbers
-                import torch.distributed as td
-                from vlfb.metrics import ava_frame_ap
-                table = dist.gather_rows(self.meter.table[:self._ava_pos])
-                parts = [None] * dist.world_size()
-                td.all_gather_object(parts, (rows, keys, boxes))
-                rows = np.concatenate([p[0] + i * self._ava_pos for i, p in enumerate(parts)])
-                keys = [k for p in parts for k in p[1]]
-                boxes = np.concatenate([p[2] for p in parts])
-                self.results = ava_frame_ap(table.contiguous(), rows, keys, boxes, self.ava_groundtruth, self.excluded_keys,
-                                            self.class_whitelist)
+            if self.world > 1:
+                # every rank holds the rows it issued: gather the tables, renumber every rank's rows to global rows
+                from vlfb.metrics import ava_frame_ap, merge_ava_ranks
+                tables, = self._gather_parts(self.meter.table)
+                table, rows, keys, boxes = merge_ava_ranks(tables, dist.gather_objects((rows, keys, boxes)), self.batch_rows)
+                self.results = ava_frame_ap(table, rows, keys, boxes, self.ava_groundtruth, self.excluded_keys, self.class_whitelist)
+                self.results["rows_seen"] = int(table.shape[0])
             else:
                 self.results = self.meter.finalize(rows, keys, boxes, self.ava_groundtruth, self.excluded_keys, self.class_whitelist)
             self.full_map = self.results["mean_ap"]
@@ -270,27 +284,35 @@ class MetricsCalculator(object):
             if is_train:
                 self.full_map = 0.0
                 return
-            _, _, cursor, mismatches = self.meter.counters()
-            n = self.meter.filled(cursor)
-            assert mismatches == 0, "labels of %d merged clip elements differ from their video's" % mismatches
-            if dist.world_size() > 1:
-                # every rank holds the videos it tested: gather the tables once and score them together
-                table = dist.gather_rows(self.meter.table[:n])
-                labels = dist.gather_rows(self.meter.labels[:n])
-                self.full_map = mean_ap_metric(table, labels.to(torch.int32))[1]
+            if self.world > 1:
+                # every rank holds the clips it issued: the stream of the single process, merged by its kernel
+                from vlfb.metrics import merge_map_ranks
+                tables, labels = self._gather_parts(self.meter.table, self.meter.labels)
+                self.merged = merge_map_ranks(tables, labels, self.batch_rows, self._map_items, self._map_total)
+                self.results = self.merged.read()
             else:
                 self.results = self.meter.read()
-                self.full_map = self.results["mean_ap"]
+            mismatches = self.results["label_mismatches"]
+            assert mismatches == 0, "labels of %d merged clip elements differ from their video's" % mismatches
+            self.full_map = self.results["mean_ap"]
         else:
             self._read_topk()
             if not is_train and self.meter.keep_rows:
-                table, labels = self.meter.kept()
-                # stack_predictions (metrics.py:147-163): every row of the split was tested, at most a batch of padding cut
-                assert table.shape[0] == self.meter.keep_rows, "%d of %d predictions were issued" % (table.shape[0], self.meter.keep_rows)
+                if self.world > 1:
+                    from vlfb.metrics import merge_keep_ranks
+                    tables, labels = self._gather_parts(self.meter.table, self.meter.labels.view(-1, 1))
+                    table, labels = merge_keep_ranks(tables, labels, self.batch_rows, int(cfg.TEST.DATASET_SIZE))
+                    labels = labels.view(-1)
+                else:
+                    table, labels = self.meter.kept()
+                    # stack_predictions (metrics.py:147-163): every row of the split was tested, at most a batch of padding cut
+                    assert table.shape[0] == self.meter.keep_rows, "%d of %d predictions were issued" % (table.shape[0], self.meter.keep_rows)
                 self.predictions = (table.cpu().numpy(), labels.cpu().numpy())
                 self.predictions_file = os.path.join(out_dir if out_dir is not None else os.getcwd(), 'epic_predictions_%s.pkl' % name)
-                with open(self.predictions_file, 'wb') as f:
-                    pickle.dump(self.predictions, f, protocol=2)
+                if dist.rank() == 0:
+                    with open(self.predictions_file, 'wb') as f:
+                        pickle.dump(self.predictions, f, protocol=2)
+                dist.barrier()                       # (no rank returns before the file is there)
 
     def get_computed_metrics(self):
         json_stats = {}

@@ -54,7 +54,7 @@ def unscope_name(blob_name):
     return blob_name[blob_name.rfind(_SCOPE_SEP) + 1:]
 
 
-def check_nan_losses(model=None):
+def check_nan_losses(model=None, sum_ranks=False):
     """NaN guard of the training loop (reference misc.py:50-58, called every iteration from
     tools/train_net.py:160 -- one FetchBlob, i.e. one host sync, per GPU per step).
 
@@ -64,7 +64,10 @@ def check_nan_losses(model=None):
 
     CONTRACT in a data-parallel job (a process group exists): the verdict is COLLECTIVE -- one all-reduce + one host sync --
     so every rank must call this, and at the same iterations; a call on rank 0 only, or at rank-dependent iterations,
-    deadlocks where the reference's per-process check was harmless."""
+    deadlocks where the reference's per-process check was harmless.
+    sum_ranks: in such a job, return the SUM over ranks of each loss (every rank's is scaled by 1 / NUM_GPUS already: the
+    reference's sum_multi_gpu_blob('loss')), the same values on every rank.  They ride on the verdict's all-reduce: no
+    further collective or synchronisation."""
     import math
     if model is not None:
         engines = [model.engine]
@@ -84,7 +87,13 @@ def check_nan_losses(model=None):
     # only through the next all-reduce, which would then wait for a rank that is gone.  Every rank calls this at the same
     # iterations, so the verdict is taken together (one int32 all-reduce) and every rank raises.
     from vlfb import dist
-    if dist.initialized():
+    if dist.initialized() and sum_ranks:
+        summed = dist.sum_floats([0.0 if bad is None else 1.0] + [0.0 if math.isnan(v) else v for v in seen],
+                                 engines[0].device if engines and engines[0] is not None else None)
+        if summed[0] > 0 and bad is None:
+            bad = "another rank"
+        seen = summed[1:]
+    elif dist.initialized():
         if not dist.all_ok(bad is None) and bad is None:
             bad = "another rank"
     if bad is not None:

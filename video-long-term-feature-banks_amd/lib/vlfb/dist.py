@@ -78,6 +78,18 @@ def sum_ints(values, device=None):
     return [int(v) for v in t.cpu().tolist()]
 
 
+def sum_floats(values, device=None):
+    """element-wise fp64 sum of a list of floats over all ranks, the same bits on every rank (the list must be equally long
+    everywhere); the list itself without a group"""
+    values = [float(v) for v in values]
+    if not initialized():
+        return values
+    dev = device if td.get_backend() == "nccl" else "cpu"
+    t = torch.tensor(values, device=dev, dtype=torch.float64)
+    td.all_reduce(t, op=td.ReduceOp.SUM)
+    return [float(v) for v in t.cpu().tolist()]
+
+
 def gather_rows(t):
     """rows of every rank's 2-D tensor (the same number on each), concatenated in rank order; `t` without a group"""
     if not initialized():
@@ -102,3 +114,22 @@ def gather_ragged(t, rows):
     parts = [torch.empty_like(src) for _ in range(world_size())]
     td.all_gather(parts, src)
     return [p[:r].to(t.device).view(t.dtype) for p, r in zip(parts, rows)]
+
+
+def gather_objects(obj):
+    """every rank's picklable `obj` as a list in rank order (small host-side records: row counts, image keys, boxes);
+    [obj] without a group"""
+    if not initialized():
+        return [obj]
+    out = [None] * world_size()
+    td.all_gather_object(out, obj)
+    return out
+
+
+def broadcast_object(obj, src=0):
+    """rank `src`'s picklable `obj` on every rank; `obj` itself without a group"""
+    if not initialized():
+        return obj
+    box = [obj]
+    td.broadcast_object_list(box, src=src)
+    return box[0]

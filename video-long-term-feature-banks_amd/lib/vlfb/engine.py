@@ -3326,7 +3326,7 @@ class Engine(object):
                         meter.kind, meter.cols, st.kernel, st.cols, want))
                 if st.labels is None:
                     n = st.rows * (1 if want == "topk" else st.cols)
-                    if meter.kind == "ava" and labels is None:
+                    if meter.kind == "ava" and labels is None and not meter.keep_labels:
                         # scored against the annotation files, not against a label blob: the merge kernel reads zeros
                         # (a net has one RoI head; the buffer is sized for the head it is made for)
                         assert len(heads) == 1, "an 'ava' meter needs `labels` when the net has %d heads" % len(heads)

@@ -286,6 +286,7 @@ _SIGS = {
     "vlfb_class_ap_voc": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _P, _I64, C.c_int, _P]),
     "vlfb_multicrop_merge": (C.c_int, [_P, C.c_int, _I64, _I64, _P, _P, _I64, _I64, C.c_int, C.c_int, C.c_int, C.c_int,
                                        _P, _P, _P, _P]),
+    "vlfb_rows_interleave": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
@@ -409,6 +410,7 @@ CLASS_AP_LDS_MAX = 8192                             # largest n vlfb_class_ap_au
 CLASS_AP_VOC_LDS_MAX = 4096                         # ... and vlfb_class_ap_voc, whose sort key is 64 bits wide
 CLASS_AP_MAX_N = 1 << 20                            # vlfb.h VLFB_CLASS_AP_MAX_N
 AVA_MAX_DET, AVA_MAX_GT = 128, 128                  # vlfb.h VLFB_AVA_MAX_DET / _GT: rows of one image vlfb_ava_match_tp holds
+ROWS_INTERLEAVE_MAX_WORLD = 64                      # vlfb.h VLFB_ROWS_INTERLEAVE_MAX_WORLD
 
 
 def query_workspace(op, arg):
@@ -419,6 +421,16 @@ def query_workspace(op, arg):
     if n < 0:
         raise VlfbError("query_workspace: %s" % lib().vlfb_last_error().decode())
     return n
+
+
+def rows_interleave(parts, part_rows, b, row_bytes, total, dst):
+    """vlfb_rows_interleave on the current stream: `parts` device addresses (ints, 0 / None for a part nothing is asked of),
+    `part_rows` their row counts, `dst` a device address.  The two host arrays are built here."""
+    world = len(parts)
+    assert len(part_rows) == world
+    addr = (C.c_void_p * max(world, 1))(*[ptr(p) for p in parts])
+    rows = (C.c_int64 * max(world, 1))(*[int(r) for r in part_rows])
+    call("vlfb_rows_interleave", addr, rows, world, int(b), int(row_bytes), int(total), ptr(dst))
 
 
 def conv_flops(d):

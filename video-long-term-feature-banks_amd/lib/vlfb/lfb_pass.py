@@ -51,20 +51,23 @@ def rank_source(source, total, rank=None, world=None):
     """the items of `source`, a generator of a `total`-iteration pass, at this rank's iterations (`rank_iterations`; default:
     vlfb.dist's rank and world).  A skipped item is drawn from the source and dropped: what the source draws from its rng
     per iteration is drawn as in the single-process walk, and since the clips are only (store, video, frames) references
-    -- fetched and decoded by the loader that consumes what is yielded -- a skipped iteration touches no frame."""
-    rank = dist.rank() if rank is None else rank
-    world = dist.world_size() if world is None else world
-    mine = set(rank_iterations(total, rank, world))
+    -- fetched and decoded by the loader that consumes what is yielded -- a skipped iteration touches no frame.
+    total None: an endless source (a training walk), the same rule without an end."""
+    rank = dist.rank() if rank is None else int(rank)
+    world = dist.world_size() if world is None else int(world)
+    assert world >= 1 and 0 <= rank < world, (rank, world)
+    if total is not None:
+        rank_iterations(total, rank, world)              # (its argument checks)
     for it, item in enumerate(source):
-        assert it < total, "the source runs past the pass's %d iterations" % total
-        if it in mine:
+        assert total is None or it < total, "the source runs past the pass's %d iterations" % total
+        if it % world == rank:
             yield item
 
 
 def check_world():
     """a pass under a process group: cfg.NUM_GPUS must be its size (the per-GPU slices come from NUM_GPUS)"""
     if dist.initialized() and dist.world_size() != int(cfg.NUM_GPUS):
-        raise hip.VlfbError("bank pass: %d ranks but cfg.NUM_GPUS = %d (the per-GPU batch and the iterations' owners come "
+        raise hip.VlfbError("a pass on %d ranks but cfg.NUM_GPUS = %d (the per-GPU batch and the iterations' owners come "
                             "from NUM_GPUS)" % (dist.world_size(), int(cfg.NUM_GPUS)))
 
 
@@ -79,7 +82,7 @@ def _on_every_rank(fn):
         dist.all_ok(False)
         raise
     if not dist.all_ok(True):
-        raise hip.VlfbError("another rank failed its part of the bank pass")
+        raise hip.VlfbError("another rank failed its part of the pass")
     return out
 
 

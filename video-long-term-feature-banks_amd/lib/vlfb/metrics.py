@@ -15,6 +15,10 @@ constant arguments that sit inside the step and add into device state; `read()` 
                ragged batches included); `finalize()` builds the image index from the host-side metadata, and
                vlfb_ava_match_tp + vlfb_class_ap_voc turn table, boxes and ground truth into the frame-mAP (ava_frame_ap)
 
+N ranks (one process per GPU): a rank's meter holds the rows that rank issued, in append mode; at finalisation the tables
+are gathered and vlfb_rows_interleave rebuilds the stream of the single-process walk (interleave_rows), which the
+single-process kernels then score (merge_map_ranks, merge_ava_ranks, merge_keep_ranks).
+
 Tie rule of top-k: rank = #{j : s_j > s_label} + #{j < label : s_j == s_label}, hit iff rank < k (include/vlfb.h).
 """
 import numpy as np
@@ -50,8 +54,12 @@ class DeviceMeter(object):
     """One device buffer: hit counters, cursor, mismatch counter, score table, label table, per-class outputs, sort
     workspace.  `update` issues kernels on the current stream and returns nothing; `read` synchronises."""
 
-    def __init__(self, kind, cols, ks=(1, 5), n_items=None, total_rows=0, device=None, keep_rows=None):
+    def __init__(self, kind, cols, ks=(1, 5), n_items=None, total_rows=0, device=None, keep_rows=None, keep_labels=False):
+        """keep_labels: an "ava" table whose label rows matter (a rank's share of a Charades pass, merged later by
+        merge_map_ranks): Engine.attach_meter then feeds it the net's label blob, not the zeros of an AVA test."""
         assert kind in ("topk", "map", "ava"), kind
+        assert not keep_labels or kind == "ava", "keep_labels belongs to an 'ava' (append-mode) meter"
+        self.keep_labels = bool(keep_labels)
         assert keep_rows is None or kind == "topk", "keep_rows belongs to a 'topk' meter (the other kinds keep their table)"
         self.keep_rows = int(keep_rows) if keep_rows is not None else 0
         if keep_rows is not None and self.keep_rows < 1:
@@ -288,6 +296,82 @@ def ava_frame_ap(table, det_rows, det_keys, det_boxes, groundtruth, excluded_key
     if return_tp:
         out["tp"] = tp.cpu().numpy()
     return out
+
+
+# ---- N ranks: every rank keeps the rows it issued; the global stream order is rebuilt at finalisation --------------------
+# Slice s of the single-process walk (b rows) belongs to rank s % world, which keeps its slices in the order it issued them.
+
+def global_row(rank, row, b, world):
+    """the row of the global stream that row `row` of rank `rank`'s own table is (numbers or numpy arrays)"""
+    return (row // b) * (b * world) + rank * b + row % b
+
+
+def rank_row(g, b, world):
+    """the inverse: global row g -> (rank, row of that rank's table); what vlfb_rows_interleave reads for row g"""
+    return (g // b) % world, (g // (b * world)) * b + g % b
+
+
+def rank_rows(total, b, world):
+    """rows of each rank's table among the first `total` rows of the global stream"""
+    full, rem = divmod(int(total), b * world)
+    return [full * b + min(max(rem - r * b, 0), b) for r in range(world)]
+
+
+def interleave_rows(parts, b, total=None):
+    """the global stream rebuilt from the ranks' tables (vlfb_rows_interleave): `parts` contiguous device tensors in rank
+    order, alike in dtype and row shape, rank r's holding the rows of its slices of `b` rows; total: rows to produce
+    (default: all of them, which then must be what `rank_rows` of their sum says).  -> a new tensor [total, ...]"""
+    world = len(parts)
+    first = parts[0]
+    assert all(p.is_cuda and p.is_contiguous() and p.dtype == first.dtype and p.shape[1:] == first.shape[1:] for p in parts)
+    have = [int(p.shape[0]) for p in parts]
+    if total is None:
+        total = sum(have)
+        if rank_rows(total, b, world) != have:
+            raise hip.VlfbError("interleave_rows: tables of %r rows are not the shares of %d ranks in a stream of %d-row "
+                                "slices" % (have, world, b))
+    row_bytes = first.element_size()
+    for d in first.shape[1:]:
+        row_bytes *= int(d)
+    out = torch.empty((int(total),) + tuple(first.shape[1:]), dtype=first.dtype, device=first.device)
+    hip.rows_interleave([p.data_ptr() if p.shape[0] else 0 for p in parts], have, b, row_bytes, total, out.data_ptr())
+    return out
+
+
+def merge_map_ranks(tables, labels, b, n_items, total_rows):
+    """Charades under N ranks: the ranks' append tables (fp32 [rows_r][cols]) and label rows (uint8, as an "ava" meter keeps
+    them) -> the "map" meter of the whole split, fed the interleaved stream in ONE vlfb_scores_merge_max, so the clip
+    merge, the cut at total_rows and the label-mismatch count are the single-process ones.  -> DeviceMeter (use read())"""
+    stream = interleave_rows(tables, b)
+    stream_labels = interleave_rows(labels, b).to(torch.int32)
+    meter = DeviceMeter("map", stream.shape[1], n_items=n_items, total_rows=total_rows, device=stream.device)
+    meter.update(stream, stream_labels)
+    return meter
+
+
+def merge_ava_ranks(tables, det, b):
+    """AVA under N ranks: the ranks' append tables and det[r] = (det_rows numbered in rank r's table, det_keys, det_boxes)
+    -> (the interleaved table, det_rows as global rows, det_keys, det_boxes), detections in global row order: the order
+    the single process names them in, which ava_image_index keeps within an image."""
+    world = len(tables)
+    table = interleave_rows(tables, b)
+    rows = np.concatenate([global_row(r, np.asarray(d[0], np.int64).reshape(-1), b, world) for r, d in enumerate(det)])
+    keys = [k for d in det for k in d[1]]
+    boxes = np.concatenate([np.asarray(d[2], np.float64).reshape(-1, 4) for d in det])
+    order = np.argsort(rows, kind="stable")
+    return table, rows[order], [keys[i] for i in order], boxes[order]
+
+
+def merge_keep_ranks(tables, labels, b, keep_rows):
+    """EPIC under N ranks: the ranks' kept prediction tables (fp32 [rows_r][cols]) and labels (int32 [rows_r]) -> the first
+    keep_rows rows of the global stream, (table, labels)"""
+    have = sum(int(t.shape[0]) for t in tables)
+    if have < keep_rows:
+        raise hip.VlfbError("merge_keep_ranks: %d of %d predictions were issued" % (have, keep_rows))
+    full = rank_rows(have, b, len(tables))
+    if full != [int(t.shape[0]) for t in tables]:
+        raise hip.VlfbError("merge_keep_ranks: tables of %r rows are not the ranks' shares %r" % ([int(t.shape[0]) for t in tables], full))
+    return interleave_rows(tables, b, keep_rows), interleave_rows(labels, b, keep_rows)
 
 
 def action_topk_hits(verb, noun, verb_labels, noun_labels, ks=(1, 5), prior=None):

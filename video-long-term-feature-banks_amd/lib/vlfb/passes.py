@@ -8,6 +8,10 @@ one table of input shapes and the one choice of loader), and the loop that walks
 The bank passes (vlfb.lfb_pass), the test pass (vlfb.test_pass) and the in-training evaluation (vlfb.train_pass.eval_pass)
 are this loop with their own `each`; the training loop steps instead of forwarding and the AVA multi-crop pass has no
 loader, so those two are not.
+
+Under a process group the counted passes -- the test pass and the evaluation -- become `run_pass_ranks`: the same walk, of which a rank forwards its
+slices (vlfb.lfb_pass.rank_source), with `each` called by every rank at every GLOBAL iteration so that a collective in
+it is reached by all of them the same number of times.
 """
 import collections
 import time
@@ -109,8 +113,21 @@ def run_pass(engine, loader, store, source, iterations=None, timer=None, each=No
     (mb.meta is the dict the source yielded).  iterations None: until the source ends; an integer: exactly that many (a
     source that ends sooner raises StopIteration).  Nothing in the loop waits for the device.  The loader is stopped
     whatever happens; then one synchronisation and the store's check_decoded (frames it decoded from JPEG bytes: none was
-    damaged).  -> iterations run"""
+    damaged).  -> iterations run
+    A COUNTED pass (`iterations` given: misc.get_total_test_iters batches of BATCH_SIZE clips, walked in per-GPU slices of
+    BATCH_SIZE // NUM_GPUS) is shared by the ranks of a process group: `run_pass_ranks`.  With NUM_GPUS > 1 and no group of
+    that size it is refused, since one process would cover 1 / NUM_GPUS of the split."""
     import torch
+    if iterations is not None:
+        from vlfb import dist, hip
+        if int(cfg.NUM_GPUS) > 1 and dist.world_size() != int(cfg.NUM_GPUS):
+            raise hip.VlfbError("a pass of %d iterations with cfg.NUM_GPUS = %d needs a process group of %d ranks, one per GPU "
+                                "(there is %s): one process walks slices of BATCH_SIZE // NUM_GPUS clips and would cover only "
+                                "1 / %d of the split" % (iterations, int(cfg.NUM_GPUS), int(cfg.NUM_GPUS),
+                                                         "one of %d" % dist.world_size() if dist.initialized() else "none",
+                                                         int(cfg.NUM_GPUS)))
+        if dist.initialized():
+            return run_pass_ranks(engine, loader, store, source, iterations, timer, each)
     ran = 0
     loader.start(source)
     try:
@@ -135,3 +152,43 @@ def run_pass(engine, loader, store, source, iterations=None, timer=None, each=No
     torch.cuda.current_stream().synchronize()
     store.check_decoded()
     return ran
+
+
+def run_pass_ranks(engine, loader, store, source, iterations, timer=None, each=None):
+    """The counted `run_pass` under a process group: `source` is the single-process walk in per-GPU slices, slice s belongs
+    to rank s % world (lfb_pass.rank_source), global iteration G is slices G * world .. G * world + world - 1, and
+    `iterations` counts GLOBAL iterations: ceil(P / world) for P slices, which is misc.get_total_test_iters.  Every rank
+    walks all of them; on each it forwards its slice if that exists -- the walk may end inside the LAST global iteration and
+    leave the higher ranks without one; rank 0 always has one -- and calls each(G, mb), mb None where it had no slice, so a
+    collective in `each` (the meter's read at LOG_PERIOD or at the last iteration) is reached by every rank alike.  The
+    outcome is agreed by all ranks (lfb_pass._on_every_rank): one failing rank fails all.  -> global iterations run"""
+    import torch
+    from vlfb import dist, lfb_pass
+    lfb_pass.check_world()
+    rank, last = dist.rank(), int(iterations) - 1
+
+    def mine():
+        loader.start(lfb_pass.rank_source(source, None))
+        try:
+            for it in range(int(iterations)):
+                if timer is not None:
+                    timer.tic()
+                try:
+                    mb = loader.next()
+                except StopIteration:
+                    if rank == 0 or it != last:
+                        raise                            # (the source is shorter than `iterations` global iterations)
+                    mb = None
+                if mb is not None:
+                    loader.deliver(mb)
+                    engine.forward()
+                if timer is not None:
+                    timer.toc()
+                if each is not None:
+                    each(it, mb)
+        finally:
+            loader.stop()
+        torch.cuda.current_stream().synchronize()
+        store.check_decoded()
+    lfb_pass._on_every_rank(mine)
+    return int(iterations)

@@ -6,6 +6,13 @@ checkpoints, precise BN, the periodic evaluation on shared parameters and the JS
 One deviation in the build order: the reference builds the test model first ("so that we don't overwrite init") because
 both nets initialise the same workspace blobs.  Here the TRAIN engine owns the parameters and the test engine is built
 second with share_params_with= it; there is one initialisation, the train engine's.
+
+N ranks (one process per GPU under a process group of cfg.NUM_GPUS ranks): the index walk is ONE walk, drawn from a generator
+that is private to the source and seeded alike everywhere, of which rank r trains on slices r, r + N, ... (lfb_pass.rank_source;
+slice g of global batch b on gpu_g); the augmentation draws come from a generator of the rank's own.  The engine reduces
+the gradients (Engine.enable_data_parallel, which first makes rank 0's parameters everybody's), the evaluation is shared
+(passes.run_pass_ranks), rank 0 writes checkpoints, the stats line and the log, and every rank returns the same
+last_checkpoint, json_stats and eval_iters.
 """
 import collections
 import logging
@@ -16,7 +23,7 @@ import numpy as np
 
 from core.config import config as cfg
 from utils import misc
-from vlfb import lfb_pass, passes
+from vlfb import dist, lfb_pass, passes
 from vlfb.passes import Timer
 
 logger = logging.getLogger(__name__)
@@ -60,13 +67,26 @@ def create_wrapper(is_train, make_store, lfb, owner=None, dtype="mix", device="c
     return Wrapper(model, engine, index, loader, store, Timer(), meter, suffix, passes.bank_video(index))
 
 
-def train_source(w, rng, aug_rng):
+def train_source(w, rng, aug_rng, walk_rng=None):
     """what the wrapper's loader is started with for training: ava.minibatch_source (shuffled per pass with `aug_rng`, a
-    numpy generator) or lfb_pass.frame_train_source (`rng`: random.Random's methods)"""
+    numpy generator, or with `walk_rng` when the walk has a generator of its own) or lfb_pass.frame_train_source (`rng`:
+    random.Random's methods)"""
     from datasets import ava
     if cfg.DATASET == 'ava':
+        if walk_rng is not None:
+            return ava.minibatch_source(w.index, w.store, walk_rng, bank=w.loader.bank, aug_rng=aug_rng)
         return ava.minibatch_source(w.index, w.store, aug_rng, bank=w.loader.bank)
     return lfb_pass.frame_train_source(w.index, w.store, rng, w.bank_video, aug_rng=aug_rng)
+
+
+def rank_train_source(w):
+    """the training source of this rank under a process group: the slices rank, rank + world, ... of the one walk whose
+    generator is seeded alike on all ranks (random.Random(RNG_SEED) for Charades / EPIC, np.random.RandomState(RNG_SEED) for
+    AVA) and consumed by the source alone; the augmentation generator np.random.RandomState(RNG_SEED + 1 + rank) is the
+    rank's own.  Skipped slices cost index arithmetic and walk draws (lfb_pass.rank_source)."""
+    aug = np.random.RandomState(cfg.RNG_SEED + 1 + dist.rank())
+    source = train_source(w, random.Random(cfg.RNG_SEED), aug, walk_rng=np.random.RandomState(cfg.RNG_SEED))
+    return lfb_pass.rank_source(source, None)
 
 
 def eval_pass(test, name='latest', curr_iter=None, rng=None):
@@ -74,11 +94,9 @@ def eval_pass(test, name='latest', curr_iter=None, rng=None):
     trained: reset, one pass over the test split, finalize_metrics / compute_and_log_best / log_final_metrics.  Charades /
     EPIC: the loop of test_one_crop; nothing is loaded and no predictions are kept.  AVA: the single-crop pass -- the
     test AvaIndex (built under AVA.FULL_EVAL = FULL_EVAL_DURING_TRAINING, DETECTION_SCORE_THRESH = _TRAIN), centre crop,
-    add_ava_batch(metadata, original_boxes) per iteration.  -> iterations run"""
+    add_ava_batch(metadata, original_boxes) per iteration.  Under a process group the pass is shared by the ranks
+    (a counted passes.run_pass is run_pass_ranks there) and every rank ends with the same figures.  -> (global) iterations run"""
     from datasets import ava
-    from vlfb import dist
-    if dist.world_size() > 1:
-        raise NotImplementedError("eval_pass: the in-training evaluation is single-process (world size %d)" % dist.world_size())
     meter, loader = test.meter, test.loader
     meter.reset()
     logger.info("=> Testing model")
@@ -91,7 +109,7 @@ def eval_pass(test, name='latest', curr_iter=None, rng=None):
         source = lfb_pass.frame_minibatch_source(test.index, test.store, test.bank_video)
 
     def score(it, mb):
-        if cfg.DATASET == 'ava' and meter.meter is not None:
+        if cfg.DATASET == 'ava' and meter.meter is not None and mb is not None:
             meter.add_ava_batch(mb.metadata[:, :2], mb.original_boxes)
         meter.calculate_and_log_all_metrics_test(it, test.timer, total, test.suffix)
     ran = passes.run_pass(test.engine, loader, test.store, source, total, test.timer, score)
@@ -113,11 +131,23 @@ def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groun
     on_eval(curr_iter, train_wrapper, test_wrapper, json_stats): called after every evaluation;
     eval_dtype: the dtype of the forward-only engines -- bank inference, the test engine, test_net (default: `dtype`, and
     "bf16", the default of the test passes, where that is "mix": `mix` is a training path).
+    Under a process group (one process per GPU): the module docstring.  TRAIN.COMPUTE_PRECISE_BN, and TRAIN.TEST_AFTER_TRAIN on
+    AVA (the multi-crop pass), are single-process and are refused before anything is built.
     -> dict(last_checkpoint=, json_stats=[...], train=, test=, bn_aux=, eval_iters=[...], final=)"""
     import torch
     from utils import checkpoints
     import utils.metrics as metrics
     from vlfb import test_pass
+
+    grouped = dist.initialized()
+    lfb_pass.check_world()
+    if grouped and cfg.TRAIN.COMPUTE_PRECISE_BN:
+        raise NotImplementedError("train: TRAIN.COMPUTE_PRECISE_BN under a process group (%d ranks): the precise-BN pass is "
+                                  "single-process; unset it" % dist.world_size())
+    if grouped and cfg.TRAIN.TEST_AFTER_TRAIN and cfg.DATASET == 'ava':
+        raise NotImplementedError("train: TRAIN.TEST_AFTER_TRAIN on AVA under a process group (%d ranks): the multi-crop test "
+                                  "pass is single-process; unset it and run test_net on the last checkpoint" % dist.world_size())
+    lead = dist.rank() == 0
 
     # Generate seed.
     misc.generate_random_seed()
@@ -173,12 +203,14 @@ def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groun
         if cfg.CHECKPOINT.RESUME or cfg.TRAIN.PARAMS_FILE:
             start_model_iter = checkpoints.load_model_from_params_file(tr.model)
         out["start_model_iter"] = start_model_iter
+        if grouped:
+            tr.engine.enable_data_parallel()                 # rank 0's parameters on every rank; reduced gradients from here on
 
         logger.info("------------- Training model... -------------")
         tr.meter.reset()
         last_checkpoint = checkpoints.get_checkpoint_resume_file()
         unlogged = []                                        # losses the guard read since the meter's last line
-        tr.loader.start(train_source(tr, rng, np.random))
+        tr.loader.start(rank_train_source(tr) if grouped else train_source(tr, rng, np.random))
         for curr_iter in range(start_model_iter, cfg.SOLVER.MAX_ITER):
             tr.model.UpdateWorkspaceLr(curr_iter)            # lr_policy.get_lr_at_iter, and the momentum correction
             tr.timer.tic()
@@ -192,14 +224,20 @@ def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groun
             evals = (curr_iter + 1) % cfg.TRAIN.EVAL_PERIOD == 0
             logs = (curr_iter + 1) % cfg.LOG_PERIOD == 0
             if logs or saves or evals or (curr_iter + 1 - start_model_iter) % 64 == 0:
-                unlogged.extend(misc.check_nan_losses(tr.model))
+                # (under a group the guard's one collective also sums the ranks' losses: sum_multi_gpu_blob('loss'))
+                unlogged.extend(misc.check_nan_losses(tr.model, sum_ranks=grouped))
 
             # Checkpoint.
             if saves:
                 if bn_aux is not None:
                     bn_aux.compute_and_update_bn_stats(curr_iter)
                 last_checkpoint = os.path.join(checkpoint_dir, 'c2_model_iter{}.pkl'.format(curr_iter + 1))
-                checkpoints.save_model_params(model=tr.model, params_file=last_checkpoint, model_iter=curr_iter)
+                if not grouped:
+                    checkpoints.save_model_params(model=tr.model, params_file=last_checkpoint, model_iter=curr_iter)
+                else:                                        # rank 0 writes; nobody goes on before the file is there
+                    lfb_pass._on_every_rank(lambda: lead and checkpoints.save_model_params(
+                        model=tr.model, params_file=last_checkpoint, model_iter=curr_iter))
+                    dist.barrier()
 
             if logs:
                 tr.meter.calculate_and_log_all_metrics_train(curr_iter, tr.timer, suffix='_train', losses=list(unlogged))
@@ -217,7 +255,10 @@ def train(make_store, dtype="mix", bank_dtype="bf16", device="cuda:0", ava_groun
                 else:
                     tr.meter.finalize_metrics(is_train=True)
                 json_stats = metrics.get_json_stats_dict(tr.meter, te.meter, curr_iter)
-                misc.log_json_stats(json_stats)
+                if grouped:                                  # (used_gpu_memory is a rank's own: the line is rank 0's)
+                    json_stats = dist.broadcast_object(json_stats)
+                if lead:
+                    misc.log_json_stats(json_stats)
                 out["json_stats"].append(json_stats)
                 if on_eval is not None:
                     on_eval(curr_iter, tr, te, json_stats)
